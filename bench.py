@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the CFG++ sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config sd15|sdxl|sdxl_lightning|sdxl_edit]
+    python bench.py --gpus N --steps K --warmup W [--config sd15|sdxl|sdxl_lightning|sdxl_edit] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic prompts: B
 independent 50-NFE DDIM-CFG++ chains (UNet at batch 2B + fused step kernel per
@@ -15,7 +15,8 @@ every rank G / N chains instead: strong scaling, BASELINE configs 3 - 5 as writt
 own prompt shard; rank 0 broadcasts the conditioning once over RCCL; nothing is exchanged
 inside the loop.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  A plain run sets up, warms up, times the K
+steps and prints the line; ``--full`` adds the roofline block, the CPU baseline and the default run's SDXL leg.
 """
 from __future__ import annotations
 
@@ -67,9 +68,15 @@ def parse():
                     help="STRONG scaling: total batch of the job, split evenly over the --gpus ranks (BASELINE configs 3/4/5 are "
                          "global batches: --config sdxl --global-batch 16, sdxl_lightning 64, sdxl_edit 8 at 1/2/4/8 GPUs)")
     ap.add_argument("--nfe", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the short SDXL 1024^2 leg the default (sd15) run appends")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the roofline block (profiled forwards), the bounded "
+                         "CPU baseline and, for the default sd15 run, the short SDXL 1024^2 leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the images the last timed step returned as DIR/<name>.npy (float32, at most "
+                         "64 MB in all: a fixed seeded sample of pixel rows when the batch is larger)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the roofline block")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the short SDXL 1024^2 leg the default (sd15) run appends")
     return ap.parse_args()
 
 
@@ -106,7 +113,8 @@ def cpu_baseline_child(cfg_name, name, nfe, lam, img):
     from oracle import sampler as O
     from oracle.unet_ref import UNetRef
     cfg = CONFIGS[cfg_name]
-    cores = os.cpu_count() or 1
+    omp = os.environ.get("OMP_NUM_THREADS", "").split(",")[0].strip()
+    cores = (int(omp) if omp.isdigit() else 0) or os.cpu_count() or 1      # a job's CPU allotment, when it names one
     threads = min(cores, 64)                 # beyond ~64 threads torch-CPU conv/GEMM stops scaling on this host
     torch.set_num_threads(threads)
     net = UNetRef(cfg, synth_state_dict(cfg, 0))
@@ -321,9 +329,31 @@ def prepare_job(solver, cfg, kind, name, B, img, lam, rank, world, dev):
     return one_job, total
 
 
-def run_workload(args, config, rank, world, dev, steps, warmup, batch=0, nfe_override=0, with_cpu_baseline=True, scaling="weak"):
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(out, directory, rank, world):
+    """--dump-outputs: the images of the last timed job - what ``solver.sample()`` hands its caller - as float32 .npy, one file per
+    rank.  A rank's share of the 64 MB budget that the images exceed is filled with a fixed seeded sample of whole pixel rows
+    (same arguments, same rows), saved as <name>_sample.npy with shape [rows, W]."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    a = out.detach().cpu().float().numpy()
+    name = "images" if world == 1 else f"images_rank{rank}"
+    budget = DUMP_LIMIT_BYTES // world - 4096             # room for the .npy header
+    if a.nbytes > budget:
+        rows = a.reshape(-1, a.shape[-1])
+        keep = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=budget // rows[0].nbytes, replace=False))
+        a, name = rows[keep], name + "_sample"
+    path = os.path.join(directory, name + ".npy")
+    np.save(path, a)
+    log(f"wrote {path} {tuple(a.shape)} float32")
+
+
+def run_workload(args, config, rank, world, dev, steps, warmup, batch=0, nfe_override=0, with_cpu_baseline=True, scaling="weak",
+                 dump_dir=""):
     """build the engine of one WORKLOADS entry, share rank 0's tile pins, warm up, time `steps` jobs between barriers
-    (max over ranks) and return the JSON fields of that workload"""
+    (max over ranks), optionally dump the last job's images, and return the JSON fields of that workload"""
     from cfgpp_amd import dist as D
     kind, name, cfg_name, nfe, lam, B, img, desc = WORKLOADS[config]
     if batch and batch != B:
@@ -391,9 +421,11 @@ def run_workload(args, config, rank, world, dev, steps, warmup, batch=0, nfe_ove
                   "conditioning_broadcast_ms": round(broadcast_ms, 3), "tile_tuning": tuning,
                   "identity": [json.loads(x) for x in D.gather_strings(D.rank_identity(dev), dev)]},
     }
-    if rank == 0 and not args.no_profile:
+    if dump_dir:
+        dump_outputs(out, dump_dir, rank, world)
+    if rank == 0 and args.full and not args.no_profile:
         result["roofline"] = roofline_block(eng, config, B, dev, PROFILE_ROUND)
-    if rank == 0 and world == 1 and with_cpu_baseline and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and with_cpu_baseline and not args.no_cpu_baseline:
         log("cpu baseline (child process, bounded) ...")
         try:
             result["cpu_baseline"] = cpu_baseline(cfg_name, name, nfe, lam, img)
@@ -462,9 +494,10 @@ def main():
         if args.global_batch % world:
             raise SystemExit(f"--global-batch {args.global_batch} does not divide over {world} rank(s)")
         batch, scaling = args.global_batch // world, "strong"
-    result = run_workload(args, args.config, rank, world, dev, args.steps, args.warmup, batch, args.nfe, scaling=scaling)
-    if args.config == "sd15" and not args.no_also and not batch and not args.nfe:
-        # BASELINE.json's metric names SD1.5 512^2 AND SDXL 1024^2: the default command also times a short SDXL leg
+    result = run_workload(args, args.config, rank, world, dev, args.steps, args.warmup, batch, args.nfe, scaling=scaling,
+                          dump_dir=args.dump_outputs)
+    if args.full and args.config == "sd15" and not args.no_also and not batch and not args.nfe:
+        # BASELINE.json's metric names SD1.5 512^2 AND SDXL 1024^2: the default --full command also times a short SDXL leg
         # (configs[2]'s per-GPU share: batch 2 per GPU, 50 NFE) - 1 warm-up job (in-situ tuning) + 2 timed jobs
         import gc
         gc.collect()

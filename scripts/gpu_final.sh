@@ -23,12 +23,12 @@ pmc_config() {   # name rows bench_config batch
 }
 echo "== PMC sd15 rows 16"; pmc_config sd15 16 sd15 8; tail -30 $OUT/pmc_sd15_summary.log | head -40
 echo "== PMC sdxl rows 4"; pmc_config sdxl 4 sdxl 2; grep -A8 '"igemm"' $OUT/pmc_sdxl_b2.json | head -12
-echo "== bench sd15 (default command)"; timeout 900 python bench.py > $OUT/bench_sd15_b8.json 2> $OUT/bench_sd15_b8.err; cat $OUT/bench_sd15_b8.json
-echo "== bench sdxl"; timeout 900 python bench.py --config sdxl --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_sdxl_b2.json 2> $OUT/bench_sdxl_b2.err; cat $OUT/bench_sdxl_b2.json
-echo "== bench sdxl_lightning"; timeout 900 python bench.py --config sdxl_lightning --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_sdxl_lightning_b8.json 2> $OUT/bench_sdxl_lightning_b8.err; cat $OUT/bench_sdxl_lightning_b8.json
-echo "== bench sdxl_edit"; timeout 900 python bench.py --config sdxl_edit --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_sdxl_edit_b1.json 2> $OUT/bench_sdxl_edit_b1.err; cat $OUT/bench_sdxl_edit_b1.json
+echo "== bench sd15 (default command)"; timeout 900 python bench.py --full > $OUT/bench_sd15_b8.json 2> $OUT/bench_sd15_b8.err; cat $OUT/bench_sd15_b8.json
+echo "== bench sdxl"; timeout 900 python bench.py --config sdxl --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/bench_sdxl_b2.json 2> $OUT/bench_sdxl_b2.err; cat $OUT/bench_sdxl_b2.json
+echo "== bench sdxl_lightning"; timeout 900 python bench.py --config sdxl_lightning --steps 2 --warmup 1 --full --no-cpu-baseline > $OUT/bench_sdxl_lightning_b8.json 2> $OUT/bench_sdxl_lightning_b8.err; cat $OUT/bench_sdxl_lightning_b8.json
+echo "== bench sdxl_edit"; timeout 900 python bench.py --config sdxl_edit --steps 1 --warmup 1 --full --no-cpu-baseline > $OUT/bench_sdxl_edit_b1.json 2> $OUT/bench_sdxl_edit_b1.err; cat $OUT/bench_sdxl_edit_b1.json
 echo "== rocprofv3 --kernel-trace --stats of the bench command"
-cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
+cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
 find $OUT/rocprof_bench -name "*kernel_stats.csv" -exec cp {} $OUT/sd15_b8_kernel_stats.csv \;
 find $OUT -name "*.csv" -size +1M -delete 2>/dev/null; find $OUT -name "*.db" -delete 2>/dev/null
 head -12 $OUT/sd15_b8_kernel_stats.csv | cut -c1-160

@@ -11,5 +11,5 @@ echo "== groupnorm A/B"; timeout 200 python scripts/bench_norm.py 2>&1 | grep "^
 echo "== igemm M=4096 shapes"; CFGS=0,1,7,9 timeout 200 python scripts/bench_igemm.py _32 2>&1 | grep -v amdgpu.ids | tee $OUT/bench_igemm_m4096.txt; CFGS=0,1,7,9 timeout 100 python scripts/bench_igemm.py l2_ 2>&1 | grep -v amdgpu.ids | tee -a $OUT/bench_igemm_m4096.txt
 echo "== profile sd15"; timeout 300 python scripts/profile_unet.py sd15 16 > $OUT/prof_sd15.txt 2>&1; head -3 $OUT/prof_sd15.txt; tail -2 $OUT/prof_sd15.txt
 echo "== profile sdxl"; timeout 400 python scripts/profile_unet.py sdxl 4 > $OUT/prof_sdxl.txt 2>&1; head -3 $OUT/prof_sdxl.txt; tail -2 $OUT/prof_sdxl.txt
-echo "== bench sd15"; timeout 600 python bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_sd15.json 2> $OUT/bench_sd15.err; cat $OUT/bench_sd15.json
+echo "== bench sd15"; timeout 600 python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_sd15.json 2> $OUT/bench_sd15.err; cat $OUT/bench_sd15.json
 du -sh $OUT

@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/r03_benchlines; mkdir -p $OUT
 export CFGPP_BENCH_VERBOSE=0
 for c in sdxl_lightning sdxl_edit; do
-  timeout 420 python bench.py --config $c --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+  timeout 420 python bench.py --full --config $c --no-cpu-baseline > $OUT/bench_$c.json 2> $OUT/bench_$c.err
   python - <<PY
 import json
 try:

@@ -24,9 +24,9 @@ pmc_config() {   # name rows bench_config batch
 }
 echo "== PMC sd15 rows 16"; pmc_config sd15 16 sd15 8; grep -A12 '"igemm"' $OUT/pmc_sd15_b8.json | head -16
 echo "== PMC sdxl rows 4"; pmc_config sdxl 4 sdxl 2; grep -A12 '"igemm"' $OUT/pmc_sdxl_b2.json | head -16
-echo "== bench (default command: sd15 b8 + the SDXL b2 leg)"; timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json
+echo "== bench (default command: sd15 b8 + the SDXL b2 leg)"; timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json
 echo "== rocprofv3 --kernel-trace --stats of the bench command"
-cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-also > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
+cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-also > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
 find $OUT/rocprof_bench -name "*kernel_stats.csv" -exec cp {} $OUT/sd15_b8_kernel_stats.csv \;
 find $OUT -name "*.csv" -size +1M -delete 2>/dev/null; find $OUT -name "*.db" -delete 2>/dev/null
 head -14 $OUT/sd15_b8_kernel_stats.csv | cut -c1-170

@@ -16,4 +16,4 @@ python scripts/pmc_per_class.py --fetch $OUT/sdxl_fetch --write $OUT/sdxl_write 
 head -12 $OUT/pmc_per_launch_class_sdxl_rows4_blocked_walk.txt | cut -c1-150
 find $OUT -name "*.csv" -size +1M -delete 2>/dev/null; find $OUT -name "*.db" -delete 2>/dev/null
 unset CFGPP_TUNE_CACHE
-echo "== bench (default)"; timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-400 $OUT/bench_default.json
+echo "== bench (default)"; timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-400 $OUT/bench_default.json

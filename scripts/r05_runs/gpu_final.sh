@@ -32,11 +32,11 @@ if [ "$WHAT" = pmc ] || [ "$WHAT" = all ]; then
   echo "== PMC sdxl rows 2 (edit b1)"; pmc_config sdxl 2 sdxl_edit 1; grep -A6 '"igemm": {' $OUT/pmc_sdxl_edit_b1.json | head -8
 fi
 if [ "$WHAT" = bench ] || [ "$WHAT" = all ]; then
-  echo "== bench (default command: sd15 b8 + the SDXL b2 leg)"; timeout 1500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json
-  echo "== bench sdxl_lightning b8"; timeout 900 python bench.py --config sdxl_lightning --no-cpu-baseline > $OUT/bench_sdxl_lightning_b8.json 2> $OUT/bench_lightning.err; cat $OUT/bench_sdxl_lightning_b8.json | cut -c1-600
-  echo "== bench sdxl_edit b1"; timeout 900 python bench.py --config sdxl_edit --no-cpu-baseline > $OUT/bench_sdxl_edit_b1.json 2> $OUT/bench_edit.err; cat $OUT/bench_sdxl_edit_b1.json | cut -c1-600
+  echo "== bench (default command: sd15 b8 + the SDXL b2 leg)"; timeout 1500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json
+  echo "== bench sdxl_lightning b8"; timeout 900 python bench.py --full --config sdxl_lightning --no-cpu-baseline > $OUT/bench_sdxl_lightning_b8.json 2> $OUT/bench_lightning.err; cat $OUT/bench_sdxl_lightning_b8.json | cut -c1-600
+  echo "== bench sdxl_edit b1"; timeout 900 python bench.py --full --config sdxl_edit --no-cpu-baseline > $OUT/bench_sdxl_edit_b1.json 2> $OUT/bench_edit.err; cat $OUT/bench_sdxl_edit_b1.json | cut -c1-600
   echo "== rocprofv3 --kernel-trace --stats of the bench command"
-  cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-also > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
+  cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT/rocprof_bench -o sd15 --output-format csv -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-also > $R/$OUT/bench_sd15_b8_under_rocprof.json 2> $R/$OUT/rocprof_bench.log; cd $R
   find $OUT/rocprof_bench -name "*kernel_stats.csv" -exec cp {} $OUT/sd15_b8_kernel_stats.csv \;
   find $OUT -name "*.csv" -size +1M -delete 2>/dev/null; find $OUT -name "*.db" -delete 2>/dev/null
   head -14 $OUT/sd15_b8_kernel_stats.csv | cut -c1-170

@@ -6,4 +6,4 @@ set -u
 python -c "from cfgpp_amd import _lib; print(_lib.build_id())"
 bash scripts/r06_runs/gpu_final.sh pmc
 OUT=gpurun_out/r06_final
-echo "== bench (default)"; timeout 1500 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | cut -c1-400
+echo "== bench (default)"; timeout 1500 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cat $OUT/bench_default.json | cut -c1-400

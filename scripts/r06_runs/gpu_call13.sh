@@ -6,4 +6,4 @@ python -c "from cfgpp_amd import _lib; print(_lib.build_id())" | tee $OUT/build_
 t0=$(date +%s)
 python3 -m pytest tests/ -x -q -m gpu -p no:cacheprovider > $OUT/pytest_driver_cmd.log 2>&1; echo "suite rc=$? in $(( $(date +%s) - t0 )) s"; tail -4 $OUT/pytest_driver_cmd.log | cut -c1-200
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; cut -c1-300 $OUT/bench_default.json

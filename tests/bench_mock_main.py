@@ -1,8 +1,8 @@
 """Test driver: ``bench.main()`` with a CPU mock engine in place of the HIP engine, so the launcher logic of
 ``python bench.py --gpus N`` (self-launch of N ranks, the world-size check, the per-rank fields of the JSON line) can run
-on a box without GPUs over gloo.  bench.py itself contains no mock path; this file replaces two of its functions.
+on CPU ranks over gloo.  bench.py itself contains no mock path; this file replaces two of its functions and pins gloo.
 
-    python tests/bench_mock_main.py --gpus 2 --steps 1 --warmup 0 --config mock --no-profile --no-cpu-baseline --no-also
+    python tests/bench_mock_main.py --gpus 2 --steps 1 --warmup 0 --config mock
 """
 import os
 import sys
@@ -16,6 +16,7 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests", "golden
 import torch  # noqa: E402
 
 import bench  # noqa: E402
+from cfgpp_amd import dist as D  # noqa: E402
 
 
 def make_solver(kind, name, cfg_name, nfe, batch, device):
@@ -37,9 +38,11 @@ def make_solver(kind, name, cfg_name, nfe, batch, device):
     return solver, TINY_SD
 
 
-bench.WORKLOADS["mock"] = ("sd", "ddim_cfg++", "tiny", 3, 0.6, 2, 64, "CPU mock engine (launcher test only)")
+bench.WORKLOADS["mock"] = ("sd", "ddim_cfg++", "tiny_sd", 3, 0.6, 2, 64, "CPU mock engine (launcher test only)")
 bench.make_solver = make_solver
 bench.device_for = lambda local_rank: torch.device("cpu")
+_init = D.init
+D.init = lambda backend=None: _init("gloo")      # CPU ranks talk over gloo even where a GPU is visible (init would pick RCCL)
 
 if __name__ == "__main__":
     bench.main()

@@ -51,6 +51,38 @@ def golden_r3():
     return g, meta
 
 
+@pytest.fixture
+def recorded_sqrt(monkeypatch):
+    """``Tensor.sqrt`` of the scheduler's alpha table as the golden vectors' recording host evaluated it.  torch's fp32 CPU
+    sqrt goes through MKL, whose result depends on the CPU: the vectors were recorded on MKL's Intel AVX-512 branch, and on
+    an AMD CPU MKL takes another branch (1 ulp apart on ~18 % of the table; MKL_CBWR does not change that).  The
+    sampler's own sigma / sqrt(alpha) arithmetic runs live, as the reference's does, so a bit-exact comparison with the
+    recordings needs the recording host's roots: cfgpp_amd/data/ddim_sqrt_tables.npz pins sqrt(a) and sqrt(1 - a) over
+    ``cat([1.0], abar)`` as recorded.  Inside a test that takes this fixture, every element of an fp32 CPU tensor that is
+    such an a or 1 - a gets that root; any other element gets torch's own.  A no-op on the recording host's branch."""
+    import numpy as np
+    import torch
+    from cfgpp_amd.schedule import alphas_cumprod, ddim_sqrt_tables
+    a = torch.cat([torch.ones(1), alphas_cumprod()])
+    roots = torch.cat(ddim_sqrt_tables()).numpy()
+    bits = torch.cat([a, 1 - a]).view(torch.int32).numpy()
+    keys, first, inv = np.unique(bits, return_index=True, return_inverse=True)
+    assert np.array_equal(roots, roots[first][inv]), "one input, two recorded roots"
+    roots = torch.from_numpy(roots[first].copy())
+    sqrt = torch.Tensor.sqrt
+
+    def recorded(x):
+        out = sqrt(x)
+        if x.dtype != torch.float32 or x.device.type != "cpu" or x.numel() == 0:
+            return out
+        xb = x.detach().contiguous().view(torch.int32).numpy().reshape(-1)
+        i = np.minimum(np.searchsorted(keys, xb), len(keys) - 1)
+        hit = torch.from_numpy(keys[i] == xb)
+        out.view(-1)[hit] = roots[torch.from_numpy(i)[hit]]
+        return out
+    monkeypatch.setattr(torch.Tensor, "sqrt", recorded)
+
+
 # ---- order of the -m gpu suite: cheap -> expensive -------------------------------------------------------------------
 # The driver runs `pytest tests/ -x -q -m gpu`: with -x a failure (or a native abort) hides every test behind it, so the
 # single-kernel parity tests go first and the real-size nets (minutes each, tens of GB of host memory) go last.

@@ -188,3 +188,50 @@ def test_bench_world_size_mismatch_is_an_error():
     p = _run_mock_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--config", "mock", "--no-profile", "--no-cpu-baseline", "--no-also"],
                         env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert p.returncode != 0 and "--gpus 2 but the job has 1 rank" in (p.stderr + p.stdout)
+
+
+# ---- what a plain `python bench.py` run does, what --full adds, --dump-outputs ----
+def _json_line(p):
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert p.returncode == 0 and len(lines) == 1, p.stderr[-2000:] + p.stdout
+    import json
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """a plain run times exactly --steps jobs, reports ms_per_step and carries none of the --full extras; --dump-outputs writes
+    the last timed job's images as float32, identical from run to run with the same arguments"""
+    import numpy as np
+    argv = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "mock"]
+    runs = []
+    for d in ("a", "b"):
+        r = _json_line(_run_mock_bench(argv + ["--dump-outputs", str(tmp_path / d)]))
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0
+        assert r["metric"] == r["unit"] == "images/sec" and r["higher_is_better"] is True and r["dtype"] == "fp16"
+        assert not {"roofline", "cpu_baseline", "also"} & set(r)
+        assert sorted(os.listdir(tmp_path / d)) == ["images.npy"]
+        runs.append(np.load(tmp_path / d / "images.npy"))
+    assert runs[0].dtype == np.float32 and runs[0].shape == (2, 3, 64, 64)
+    assert np.array_equal(runs[0], runs[1])
+
+
+def test_bench_full_adds_the_cpu_baseline():
+    """--full keeps what the default run measured before it became lean (here: the CPU baseline; --no-profile because the mock
+    engine has no profiler)"""
+    r = _json_line(_run_mock_bench(["--gpus", "1", "--steps", "1", "--warmup", "0", "--config", "mock", "--full", "--no-profile"]))
+    assert "roofline" not in r and r["cpu_baseline"]["value"] > 0, r.get("cpu_baseline")
+
+
+def test_bench_dump_outputs_samples_rows_above_the_budget(tmp_path, monkeypatch):
+    """images above the 64 MB budget are written as a fixed seeded sample of whole pixel rows that fits it"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 20)
+    img = torch.rand((2, 3, 256, 256), generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(img, str(tmp_path / "a"), 0, 1)
+    bench.dump_outputs(img, str(tmp_path / "b"), 0, 1)
+    a, b = (np.load(tmp_path / d / "images_sample.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and a.shape[1] == 256 and 0 < a.nbytes <= (1 << 20) and np.array_equal(a, b)
+    rows = img.reshape(-1, 256).numpy()
+    assert all((rows == r).all(axis=1).any() for r in a)

@@ -242,7 +242,7 @@ def test_sd_kdiff_trajectory(golden, name, tag, nfe, lam, monkeypatch):
                                               ("dpm++_2m_cfgpp", "G4/xl_dpm2m_cfgpp", 20, 0.6),
                                               ("dpm++_2m_cfgpp_lightning", "G4/xl_light_dpm2m_cfgpp", 4, 1.0),
                                               ("euler_cfg++", "G4/xl_euler_cfgpp", 10, 0.6)])
-def test_sdxl_trajectory(golden, name, tag, nfe, lam):
+def test_sdxl_trajectory(golden, recorded_sqrt, name, tag, nfe, lam):
     g, meta = golden
     s, eng = make_xl(name, nfe)
     rec = Rec()
