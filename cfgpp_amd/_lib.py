@@ -43,6 +43,7 @@ PROTOTYPES = {
     "cfgpp_build_id": (C.c_char_p, []),
     "cfgpp_step_ddim": (_I, [_P, _P, _P, _P, _I, _F, _F, _F, _F, _F, _I, _I, _L, _P]),
     "cfgpp_step_ddim_h": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _L, _P]),
+    "cfgpp_step_ddim_masked": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _P, _P, _P, _F, _F, _I, _L, _P]),
     "cfgpp_kdiff_input": (_I, [_P, _P, _F, _I, _L, _P]),
     "cfgpp_step_kdiff": (_I, [_P, _P, _P, _P, _P, C.POINTER(C.c_float), _I, _I, _I, _I, _L, _P]),
     "cfgpp_kdiff_denoise": (_I, [_P, _P, _P, _F, _F, _P, _P, _L, _P]),
@@ -53,6 +54,7 @@ PROTOTYPES = {
     "cfgpp_unet_missing": (_I, [_P]),
     "cfgpp_unet_finalize": (_I, [_P]),
     "cfgpp_unet_set_context": (_I, [_P, _P, _I, _I, _P, _P, _I, _P]),
+    "cfgpp_unet_image_condition": (_I, [_P, _P, _I, _P]),
     "cfgpp_unet_forward": (_I, [_P, _P, _I, _I, _F, _P, _I, _P]),
     "cfgpp_sample_graph_ddim": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, C.POINTER(C.c_float), _I, _F, _I, _I, _P]),
     "cfgpp_unet_profile": (_I, [_P, _P, _I, _I, _F, _P, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p, _L]),
@@ -92,6 +94,7 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_attention_prepare_vt": (_I, [_P, _I, _I, _I, _P]),
     "cfgpp_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_vae_posterior": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "cfgpp_op_conv_out": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_out_ex": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

@@ -5,6 +5,7 @@ The reference builds everything with ``StableDiffusionPipeline.from_pretrained(m
 copy of such a checkpoint (no hub access here) the same components map onto this package as
 
     <dir>/unet/diffusion_pytorch_model.safetensors          -> unet_weights=   (HIP UNet engine)
+    <dir>/unet/config.json, "in_channels": 9                -> unet_config=    (SD15_INPAINT / SDXL_INPAINT: an inpaint checkpoint)
     <dir>/vae/diffusion_pytorch_model.safetensors           -> vae_weights=    (HIP VAE engine; SD1.5 only)
     <dir>/vae_fp16_fix/diffusion_pytorch_model.safetensors  -> vae_weights=    (SDXL: the reference REPLACES the pipeline's VAE with
                                                                madebyollin/sdxl-vae-fp16-fix, latent_sdxl.py:44,396 - the stock
@@ -70,6 +71,14 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
         kw["unet_weights"] = unet
     else:
         missing.append("unet")
+    ucfg = os.path.join(d, "unet", "config.json")
+    if os.path.exists(ucfg):            # an inpaint checkpoint's UNet takes 9 input channels (latent, mask, masked-image latent)
+        import json
+        with open(ucfg) as f:
+            cin = int(json.load(f).get("in_channels", 4))
+        if cin == 9:
+            from .unet_config import SD15_INPAINT, SDXL_INPAINT
+            kw["unet_config"] = SDXL_INPAINT if sdxl else SD15_INPAINT
     if vae:
         kw["vae_weights"] = vae
     else:

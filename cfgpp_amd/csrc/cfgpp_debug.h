@@ -58,6 +58,11 @@ void cfgpp_attention_set_stagger(int sleeps);
 void cfgpp_attention_set_cross(int on);
 int cfgpp_op_conv_in(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                      int R, int zB, int Cin, int H, int W, int Cout, void* stream);
+/* conv_in of an inpaint UNet: input channels 0..Cz-1 from z (row r % zB), Cz..Cz+Cc-1 from the fp16 condition
+ * [cond_rows][Cc][H][W] (row (r % zB) % cond_rows), Cz + Cc <= 16; w [9*(Cz+Cc)][Cout] fp32 (k = tap*Cin + ci).
+ * cond = NULL is cfgpp_op_conv_in. */
+int cfgpp_op_conv_in_cond(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, void* out, const float* w,
+                          const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream);
 /* quant_conv (1x1, 8->8) + DiagonalGaussian posterior on the encoder's 8-channel conv_out (fp32 NCHW). */
 int cfgpp_op_vae_posterior(const float* conv_out, const float* qw, const float* qb, const float* noise, float* z,
                            float* moments, int B, int HW, float scale, void* stream);

@@ -8,22 +8,29 @@
 namespace {
 
 // ---------------------------------------------------------------------------
-// conv_in: 3x3 pad 1, Cin <= 8, NCHW latent (fp32 or fp16) -> halo-padded NHWC fp16.
-// Output row r reads latent sample (r % zB): the reference's torch.cat([zt]*2)
-// (latent_diffusion.py:153) is an index computation here (K13 eliminated).
-// w: [9*Cin][Cout] fp32 (k = tap*Cin + ci), bias [Cout] fp32.
+// conv_in: 3x3 pad 1, Cz + Cc <= 16 input channels -> halo-padded NHWC fp16.
+// Channels 0..Cz-1 come from the NCHW latent z (fp32 or fp16): output row r reads latent sample
+// (r % zB) - the reference's torch.cat([zt]*2) (latent_diffusion.py:153) is an index computation here
+// (K13 eliminated).  Channels Cz..Cz+Cc-1 come from the step-invariant fp16 condition [cond_rows][Cc][H][W]
+// of an inpaint UNet (mask + masked-image latent), row (r % zB) % cond_rows: diffusers'
+// torch.cat([latent_model_input, mask, masked_image_latents], dim=1) is an index computation as well.
+// cond == null: Cc = 0 and the arithmetic is the plain 4-channel (or VAE) conv_in's.
+// w: [9*Cin][Cout] fp32 (k = tap*Cin + ci, Cin = Cz + Cc), bias [Cout] fp32.
 // ---------------------------------------------------------------------------
 template <typename TIN>
 __global__ void __launch_bounds__(256)
-conv_in_kernel(const TIN* __restrict__ z, half_t* __restrict__ out, const float* __restrict__ w,
-               const float* __restrict__ bias, int R, int zB, int Cin, int H, int W, int Cout,
+conv_in_kernel(const TIN* __restrict__ z, const half_t* __restrict__ cond, int Cc, int cond_rows,
+               half_t* __restrict__ out, const float* __restrict__ w,
+               const float* __restrict__ bias, int R, int zB, int Cz, int H, int W, int Cout,
                const float* __restrict__ pre_w, const float* __restrict__ pre_b, float in_scale) {
     constexpr int TP = 16;                 // pixels per block
-    __shared__ float patch[TP][9 * 8];
+    __shared__ float patch[TP][9 * 16];
     const int r = blockIdx.y;
     const int p0 = blockIdx.x * TP;
     const int HW = H * W;
     const int zb = r % zB;
+    const int cb = cond ? zb % cond_rows : 0;
+    const int Cin = Cz + Cc;
     const int K = 9 * Cin;
     for (int i = threadIdx.x; i < TP * K; i += blockDim.x) {
         const int tp = i / K, k = i - tp * K;
@@ -33,15 +40,17 @@ conv_in_kernel(const TIN* __restrict__ z, half_t* __restrict__ out, const float*
         if (p < HW) {
             const int y = p / W + tap / 3 - 1, x = p % W + tap % 3 - 1;
             if (y >= 0 && y < H && x >= 0 && x < W) {
-                if (pre_w) {
+                if (ci >= Cz) {
+                    v = (float)cond[((long)(cb * Cc + ci - Cz) * H + y) * W + x];
+                } else if (pre_w) {
                     // pointwise pre-conv folded in (VAE: z / scaling_factor -> post_quant_conv 1x1), applied to
                     // in-bounds pixels only so the zero padding of the 3x3 conv stays zero
                     float acc = pre_b ? pre_b[ci] : 0.f;
-                    for (int j = 0; j < Cin; ++j)
-                        acc += pre_w[ci * Cin + j] * (float)(half_t)((float)z[((long)(zb * Cin + j) * H + y) * W + x] * in_scale);
+                    for (int j = 0; j < Cz; ++j)
+                        acc += pre_w[ci * Cz + j] * (float)(half_t)((float)z[((long)(zb * Cz + j) * H + y) * W + x] * in_scale);
                     v = acc;
                 } else {
-                    v = (float)z[((long)(zb * Cin + ci) * H + y) * W + x] * in_scale;
+                    v = (float)z[((long)(zb * Cz + ci) * H + y) * W + x] * in_scale;
                 }
             }
         }
@@ -330,6 +339,26 @@ int cfgpp_op_vae_posterior(const float* conv_out, const float* qw, const float* 
     return 0;
 }
 
+// z: the first Cz input channels; cond (fp16 [cond_rows][Cc][H][W]) or null: the last Cc (inpaint UNets)
+int cfgpp_op_conv_in_cond(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, void* out, const float* w,
+                          const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream) {
+    CFGPP_REQUIRE(Cz >= 1 && Cz <= 8, "conv_in: Cin=%d (<= 8)", Cz);
+    CFGPP_REQUIRE(!cond || (Cc >= 1 && Cz + Cc <= 16 && cond_rows > 0), "conv_in: condition of %d channels x %d rows on %d latent channels (Cin <= 16)",
+                  Cc, cond_rows, Cz);
+    CFGPP_REQUIRE(z && out && w && R > 0 && zB > 0, "conv_in: bad args");
+    if (!cond) { Cc = 0; cond_rows = 1; }
+    dim3 grid(cdiv((long)H * W, 16), R);
+    hipStream_t s = (hipStream_t)stream;
+    if (z_is_half)
+        hipLaunchKernelGGL(conv_in_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)z, (const half_t*)cond, Cc, cond_rows, (half_t*)out, w, bias,
+                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f);
+    else
+        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (const half_t*)cond, Cc, cond_rows, (half_t*)out, w, bias,
+                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 int cfgpp_op_conv_in_ex(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                         int R, int zB, int Cin, int H, int W, int Cout, const float* pre_w, const float* pre_b,
                         float in_scale, void* stream) {
@@ -338,9 +367,11 @@ int cfgpp_op_conv_in_ex(const void* z, int z_is_half, void* out, const float* w,
     dim3 grid(cdiv((long)H * W, 16), R);
     hipStream_t s = (hipStream_t)stream;
     if (z_is_half)
-        hipLaunchKernelGGL(conv_in_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)z, (half_t*)out, w, bias, R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
+        hipLaunchKernelGGL(conv_in_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)z, (const half_t*)nullptr, 0, 1, (half_t*)out, w, bias,
+                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
     else
-        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (half_t*)out, w, bias, R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
+        hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (const half_t*)nullptr, 0, 1, (half_t*)out, w, bias,
+                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -88,6 +88,53 @@ ddim_step_kernel(float* __restrict__ z, float* __restrict__ z0t_out,
     }
 }
 
+// MASKED variant for inpainting with an ordinary (4-channel) UNet: the fp32-latent / fp16-eps update above, then in the same
+// pass the blend of diffusers' StableDiffusionInpaintPipeline.__call__ (`if num_channels_unet == 4:` branch):
+//     proper  = a*src + b*noise                    scheduler.add_noise(image_latents, noise, t_next) in fp32
+//     z       = m ? z_new : proper                 (1 - mask) * init_latents_proper + mask * latents
+//     z0t_out = m ? z0t   : src
+// m = mask[b][p] (uint8, 0 / 1: binarized on the host) broadcast over the 4 channels; src fp16 and noise fp32 [B][4][hw].
+// For a binary mask the select is the reference's arithmetic blend (up to the sign of a zero).  hw % 4 == 0, so the 4
+// elements of one float4 share batch row and channel and read 4 consecutive mask bytes.
+__global__ void __launch_bounds__(256)
+ddim_step_masked_kernel(float* __restrict__ z, float* __restrict__ z0t_out,
+                        const half_t* __restrict__ eps_uc, const half_t* __restrict__ eps_c,
+                        float lam, float c1, float c2, float c3, float c4, int tweedie_uc, int renoise_uc,
+                        const unsigned char* __restrict__ mask, const half_t* __restrict__ src, const float* __restrict__ noise,
+                        float a, float b, long hw4, long n4) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long stride = (long)gridDim.x * blockDim.x;
+    for (; i < n4; i += stride) {
+        const float4 zv = reinterpret_cast<const float4*>(z)[i];
+        const half4_t ua = reinterpret_cast<const half4_t*>(eps_uc)[i];
+        const half4_t ub = reinterpret_cast<const half4_t*>(eps_c)[i];
+        const half4_t sv = reinterpret_cast<const half4_t*>(src)[i];
+        const float4 nv = reinterpret_cast<const float4*>(noise)[i];
+        const long bi = i / (4 * hw4), pi = i - bi * 4 * hw4;          // batch row, float4 index inside the row
+        const uchar4 mv = reinterpret_cast<const uchar4*>(mask)[bi * hw4 + pi % hw4];
+        const float zi[4] = {zv.x, zv.y, zv.z, zv.w}, nz[4] = {nv.x, nv.y, nv.z, nv.w};
+        const bool mk[4] = {mv.x != 0, mv.y != 0, mv.z != 0, mv.w != 0};
+        float z0[4], zn[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float uc = (float)ua[k], cc = (float)ub[k];
+            const float hat = cfg_mix_h(uc, cc, lam);
+            const float A = tweedie_uc ? uc : hat;
+            const float B = renoise_uc ? uc : hat;
+            const float pa = h_round(__fmul_rn(A, c1));
+            const float pb = h_round(__fmul_rn(B, c4));
+            const float z0k = div_as_ref(__fsub_rn(zi[k], pa), c2);
+            const float znk = __fadd_rn(__fmul_rn(c3, z0k), pb);
+            const float s = (float)sv[k];
+            const float proper = __fadd_rn(__fmul_rn(a, s), __fmul_rn(b, nz[k]));
+            z0[k] = mk[k] ? z0k : s;
+            zn[k] = mk[k] ? znk : proper;
+        }
+        reinterpret_cast<float4*>(z0t_out)[i] = make_float4(z0[0], z0[1], z0[2], z0[3]);
+        reinterpret_cast<float4*>(z)[i] = make_float4(zn[0], zn[1], zn[2], zn[3]);
+    }
+}
+
 // fp16 LATENT variant: the inversion / edit paths start from `vae.encode(...)`, which is fp16 under the
 // reference's fp16 pipeline, so zt stays fp16 through the inversion AND the regeneration loop and every op
 // rounds to fp16 (latent_diffusion.py:168-180,527-541; latent_sdxl.py:307-318,989-1011):
@@ -247,6 +294,19 @@ int cfgpp_step_ddim(void* z, void* z0t_out, const void* eps_uc, const void* eps_
     else
         hipLaunchKernelGGL(ddim_step_kernel<false>, dim3(grid_for(n4)), dim3(256), 0, s, (float*)z, (float*)z0t_out,
                            eps_uc, eps_c, lam, c1, c2, c3, c4, tweedie_uc, renoise_uc, n4, (const float*)nullptr);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int cfgpp_step_ddim_masked(void* z, void* z0t_out, const void* eps_uc, const void* eps_c, float lam, float c1, float c2, float c3,
+                           float c4, int tweedie_uc, int renoise_uc, const void* mask, const void* src, const void* noise, float a,
+                           float b, int B, long hw, void* stream) {
+    CFGPP_REQUIRE(B > 0 && hw > 0 && (hw % 4) == 0, "cfgpp_step_ddim_masked: B=%d hw=%ld (hw must be a positive multiple of 4)", B, hw);
+    CFGPP_REQUIRE(z && z0t_out && eps_uc && eps_c && mask && src && noise, "cfgpp_step_ddim_masked: null pointer");
+    const long n4 = (long)B * 4 * hw / 4;
+    hipLaunchKernelGGL(ddim_step_masked_kernel, dim3(grid_for(n4)), dim3(256), 0, (hipStream_t)stream, (float*)z, (float*)z0t_out,
+                       (const half_t*)eps_uc, (const half_t*)eps_c, lam, c1, c2, c3, c4, tweedie_uc, renoise_uc,
+                       (const unsigned char*)mask, (const half_t*)src, (const float*)noise, a, b, hw / 4, n4);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }

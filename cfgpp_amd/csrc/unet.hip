@@ -20,10 +20,13 @@ struct cfgpp_unet : EngineBase {
     // forward-time inputs (pointers patched per call)
     const void* in_z = nullptr; int in_z_half = 0; int in_z_rows = 0; float in_t = 0.f; void* out_eps = nullptr;
     const float* in_t_dev = nullptr;        // non-null: the timestep sinusoid reads *in_t_dev (graph replay) instead of in_t
+    // inpaint UNets (in_channels > out_channels): the step-invariant extra input channels (mask + masked-image latent), fp16
+    // [cond_rows][in - out][H][W] in an engine-owned buffer whose address never changes (captured graphs stay valid)
+    half_t* d_cond = nullptr; int cond_rows = 0;
     // whole-step graph replay (cfgpp_sample_graph_ddim): per-step scalar table, current-step block, step counter, the one cached graph
     float* d_step_tab = nullptr; int step_tab_cap = 0; float* d_step_cur = nullptr; int* d_step_idx = nullptr;
     hipStream_t cap_stream = nullptr;
-    struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; };
+    struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; int cond_rows; };
     struct Graph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<Graph> graphs;              // most recently used last; at most 4 (an invert + edit job alternates between two)
     int tuned_serial = 0;                   // bumps whenever the pins of the current batch change (a graph bakes the tiles it captured)
@@ -129,6 +132,11 @@ cfgpp_unet* cfgpp_unet_create(const cfgpp_unet_config* cfg, int device_id) {
         }
     }
     if (cfg->cross_attention_dim % 64 != 0) { cfgpp_set_error("unet_create: cross_attention_dim must be a multiple of 64"); return nullptr; }
+    if (cfg->in_channels > cfg->out_channels && cfg->in_channels > 16) {
+        cfgpp_set_error("unet_create: in_channels=%d out_channels=%d (an inpaint UNet takes at most 16 input channels)", cfg->in_channels,
+                        cfg->out_channels);
+        return nullptr;
+    }
     if ((cfg->sample_h % (1 << (cfg->num_levels - 1))) || (cfg->sample_w % (1 << (cfg->num_levels - 1)))) {
         cfgpp_set_error("unet_create: sample size must be divisible by 2^(levels-1)"); return nullptr;
     }
@@ -409,9 +417,19 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
             r[(size_t)(t * Ci + i) * c0 + o] = pw->f[((size_t)o * Ci + i) * 9 + t];
         float* dw = B.upload(r); float* db = B.upload(pb->f);
         cfgpp_unet* uu = u; half_t* xp = x.p; const int HH = H, WW = W;
-        u->plan.push_back([=](hipStream_t s, int rows) {
-            return cfgpp_op_conv_in(uu->in_z, uu->in_z_half, xp, dw, db, rows, uu->in_z_rows, Ci, HH, WW, c0, s);
-        });
+        if (Ci > c.out_channels) {          // inpaint UNet: latent channels from z, the rest from the condition buffer
+            const int Cz = c.out_channels, Cc = Ci - Cz;
+            u->d_cond = (half_t*)u->dmalloc((size_t)R * Cc * H * W * sizeof(half_t));
+            CFGPP_REQUIRE(u->d_cond, "finalize: hipMalloc failed");
+            u->plan.push_back([=](hipStream_t s, int rows) {
+                return cfgpp_op_conv_in_cond(uu->in_z, uu->in_z_half, uu->d_cond, uu->cond_rows, Cc, xp, dw, db, rows, uu->in_z_rows, Cz,
+                                             HH, WW, c0, s);
+            });
+        } else {
+            u->plan.push_back([=](hipStream_t s, int rows) {
+                return cfgpp_op_conv_in(uu->in_z, uu->in_z_half, xp, dw, db, rows, uu->in_z_rows, Ci, HH, WW, c0, s);
+            });
+        }
     }
     std::vector<Tensor> skips; skips.push_back(x);
     // ---- down ----
@@ -508,12 +526,27 @@ int cfgpp_unet_set_context(cfgpp_unet* u, const void* ehs, int rows, int tokens,
     return 0;
 }
 
+int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, void* stream) {
+    CFGPP_REQUIRE(u && u->finalized, "image_condition: engine not finalized");
+    CFGPP_REQUIRE(u->cfg.in_channels > u->cfg.out_channels && u->d_cond,
+                  "image_condition: this UNet takes %d input channels for %d latent channels - no image condition (not an inpaint UNet)",
+                  u->cfg.in_channels, u->cfg.out_channels);
+    CFGPP_REQUIRE(cond && cond_rows > 0 && cond_rows <= u->cfg.max_rows, "image_condition: cond_rows=%d (1 .. %d)", cond_rows, u->cfg.max_rows);
+    const size_t bytes = (size_t)cond_rows * (u->cfg.in_channels - u->cfg.out_channels) * u->cfg.sample_h * u->cfg.sample_w * sizeof(half_t);
+    CFGPP_HIP_CHECK(hipMemcpyAsync(u->d_cond, cond, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    u->cond_rows = cond_rows;
+    return 0;
+}
+
 int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, float t, void* eps_out, int rows,
                        void* stream) {
     CFGPP_REQUIRE(u && u->finalized, "forward: context not finalized");
     CFGPP_REQUIRE(u->ctx_set, "forward: set_context has not been called");
     CFGPP_REQUIRE(z && eps_out && z_rows > 0 && rows > 0 && rows <= u->cfg.max_rows, "forward: bad args (rows=%d max=%d)", rows, u->cfg.max_rows);
     CFGPP_REQUIRE(rows == u->ctx_rows, "forward: rows=%d but context was set for %d rows", rows, u->ctx_rows);
+    CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
+                  "forward: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",
+                  u->cfg.in_channels, z_rows, u->cond_rows);
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->in_t_dev = nullptr; u->out_eps = eps_out;
     if (u->tuned_rows != rows && igemm_autotune_enabled()) {      // first forward at this batch: in-situ tile tuning
         int e = u->tune_plan((hipStream_t)stream, rows); if (e) return e;
@@ -539,7 +572,10 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
     CFGPP_REQUIRE(z && z0t && eps && eps_uc && eps_c && host_steps && n_steps > 0 && z_rows > 0, "sample_graph: bad args");
     CFGPP_REQUIRE(rows == u->ctx_rows && rows <= u->cfg.max_rows, "sample_graph: rows=%d but context was set for %d rows", rows, u->ctx_rows);
     hipStream_t s = (hipStream_t)stream;
-    const long n = (long)z_rows * u->cfg.in_channels * u->cfg.sample_h * u->cfg.sample_w;
+    CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
+                  "sample_graph: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",
+                  u->cfg.in_channels, z_rows, u->cond_rows);
+    const long n = (long)z_rows * u->cfg.out_channels * u->cfg.sample_h * u->cfg.sample_w;
     if (!u->d_step_cur) {
         u->d_step_cur = (float*)u->dmalloc(8 * sizeof(float));
         u->d_step_idx = (int*)u->dmalloc(sizeof(int));
@@ -553,11 +589,11 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
         CFGPP_REQUIRE(u->d_step_tab, "sample_graph: out of device memory");
         u->step_tab_cap = cap;
     }
-    const cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0};
+    const cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
     auto same = [&](const cfgpp_unet::GraphKey& k) {
         return k.z == want.z && k.z0t == want.z0t && k.eps == want.eps && k.euc == want.euc && k.ec == want.ec && k.z_half == want.z_half &&
                k.z_rows == want.z_rows && k.rows == want.rows && k.tw == want.tw && k.rn == want.rn && k.lam == want.lam && k.n == want.n &&
-               k.tuned_serial == u->tuned_serial;
+               k.tuned_serial == u->tuned_serial && k.cond_rows == want.cond_rows;
     };
     int hit = -1;
     for (size_t i = 0; i < u->graphs.size(); ++i) if (same(u->graphs[i].key)) hit = (int)i;

@@ -66,6 +66,36 @@ def step_ddim(z: torch.Tensor, z0t_out: torch.Tensor, eps_uc: torch.Tensor, eps_
           "cfgpp_step_ddim")
 
 
+def step_ddim_masked(z: torch.Tensor, z0t_out: torch.Tensor, eps_uc: torch.Tensor, eps_c: torch.Tensor, lam: float,
+                     coeffs: Tuple[float, float, float, float], tweedie_uc: bool, renoise_uc: bool, mask: torch.Tensor,
+                     src: torch.Tensor, noise: torch.Tensor, a: float, b: float):
+    """:func:`step_ddim` on an fp32 latent with fp16 eps, blended in the same pass with the forward-noised source
+    (include/cfgpp.h: cfgpp_step_ddim_masked): ``z = where(mask, z_new, a*src + b*noise)``, ``z0t_out = where(mask, z0t, src)``.
+    z / z0t_out / noise fp32 [B,4,h,w], eps / src fp16 [B,4,h,w], mask bool or uint8 [B,1,h,w] (or [B,h,w]), nonzero = repaint."""
+    lib = _lib.load()
+    for n, t in (("z", z), ("z0t_out", z0t_out), ("eps_uc", eps_uc), ("eps_c", eps_c), ("mask", mask), ("src", src),
+                 ("noise", noise)):
+        _require_cuda(t, n)
+    if z.dtype != torch.float32 or z0t_out.dtype != torch.float32 or noise.dtype != torch.float32:
+        raise CfgppError("step_ddim_masked: z, z0t_out and noise must be fp32")
+    if eps_uc.dtype != torch.float16 or eps_c.dtype != torch.float16 or src.dtype != torch.float16:
+        raise CfgppError("step_ddim_masked: eps and src must be fp16")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise CfgppError("step_ddim_masked: mask must be bool or uint8 (binarized)")
+    if z.dim() != 4 or tuple(z.shape[1:2]) != (4,):
+        raise CfgppError(f"step_ddim_masked: z shape {tuple(z.shape)} is not [B, 4, h, w]")
+    B, hw = int(z.shape[0]), int(z.shape[2]) * int(z.shape[3])
+    for n, t in (("z0t_out", z0t_out), ("eps_uc", eps_uc), ("eps_c", eps_c), ("src", src), ("noise", noise)):
+        if tuple(t.shape) != tuple(z.shape):
+            raise CfgppError(f"step_ddim_masked: {n} shape {tuple(t.shape)} != z shape {tuple(z.shape)}")
+    if mask.numel() != B * hw:
+        raise CfgppError(f"step_ddim_masked: mask has {mask.numel()} elements for B={B} x hw={hw}")
+    c1, c2, c3, c4 = (float(x) for x in coeffs)
+    check(lib.cfgpp_step_ddim_masked(z.data_ptr(), z0t_out.data_ptr(), eps_uc.data_ptr(), eps_c.data_ptr(), float(lam), c1, c2, c3, c4,
+                                     int(bool(tweedie_uc)), int(bool(renoise_uc)), mask.data_ptr(), src.data_ptr(), noise.data_ptr(),
+                                     float(a), float(b), B, hw, _stream_ptr(z)), "cfgpp_step_ddim_masked")
+
+
 def kdiff_input(x: torch.Tensor, xc_out: torch.Tensor, s: float, mode: int):
     lib = _lib.load()
     _require_cuda(x, "x")
@@ -149,6 +179,8 @@ class HipUNet:
             raise CfgppError("cfgpp_unet_create failed: " + _lib.last_error())
         self._keep = {}          # tensors the engine holds raw pointers to
         self.finalized = False
+        self.latent_channels = cfg.out_channels      # z carries these; an inpaint UNet's other inputs come from image_condition
+        self.cond_channels = cfg.in_channels - cfg.out_channels
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -206,6 +238,19 @@ class HipUNet:
         check(self.lib.cfgpp_unet_set_context(self._h, ehs.data_ptr(), rows, tokens, _ptr(te), _ptr(ti), cond_rows,
                                               _stream_ptr(ehs)), "cfgpp_unet_set_context")
 
+    def image_condition(self, cond: torch.Tensor):
+        """inpaint UNets only: the step-invariant extra input channels ``cond`` [1 or z_rows, in - out, H, W] (mask, masked-image
+        latent: diffusers' channel order), copied into the engine (include/cfgpp.h: cfgpp_unet_image_condition)."""
+        if self.cond_channels <= 0:
+            raise CfgppError(f"image_condition: {self.cfg.name} takes no image condition (in_channels == out_channels)")
+        dev = torch.device("cuda", self.device)
+        cond = cond.to(device=dev, dtype=torch.float16).contiguous()
+        if cond.dim() != 4 or tuple(cond.shape[1:]) != (self.cond_channels, self.H, self.W):
+            raise CfgppError(f"image_condition: cond shape {tuple(cond.shape)} != [*, {self.cond_channels}, {self.H}, {self.W}]")
+        check(self.lib.cfgpp_unet_image_condition(self._h, cond.data_ptr(), int(cond.shape[0]), _stream_ptr(cond)),
+              "cfgpp_unet_image_condition")
+        self._keep["cond"] = cond          # the copy is asynchronous on the current stream: keep the source alive
+
     # -- forward -----------------------------------------------------------------
     def forward(self, z: torch.Tensor, t: float, eps_out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """eps[rows,4,H,W] fp16 = UNet(z[row % z_rows], t); rows were fixed by set_context."""
@@ -213,8 +258,8 @@ class HipUNet:
         if z.dtype not in (torch.float16, torch.float32):
             raise CfgppError("forward: z must be fp16 or fp32")
         zr = int(z.shape[0])
-        if tuple(z.shape[1:]) != (self.cfg.in_channels, self.H, self.W):
-            raise CfgppError(f"forward: z shape {tuple(z.shape)} != [*, {self.cfg.in_channels}, {self.H}, {self.W}]")
+        if tuple(z.shape[1:]) != (self.latent_channels, self.H, self.W):
+            raise CfgppError(f"forward: z shape {tuple(z.shape)} != [*, {self.latent_channels}, {self.H}, {self.W}]")
         rows = self.rows
         if rows % zr != 0:
             raise CfgppError(f"forward: rows={rows} is not a multiple of z rows={zr}")
@@ -232,7 +277,7 @@ class HipUNet:
             _require_cuda(t, n)
         if z.dtype != z0t.dtype or z.dtype not in (torch.float16, torch.float32) or eps.dtype != torch.float16:
             raise CfgppError("sample_graph_ddim: z / z0t must both be fp32 or both fp16, eps fp16")
-        if tuple(z.shape[1:]) != (self.cfg.in_channels, self.H, self.W) or z.shape != z0t.shape:
+        if tuple(z.shape[1:]) != (self.latent_channels, self.H, self.W) or z.shape != z0t.shape:
             raise CfgppError(f"sample_graph_ddim: z shape {tuple(z.shape)}")
         if int(eps.shape[0]) != self.rows or self.rows % int(z.shape[0]) != 0:
             raise CfgppError(f"sample_graph_ddim: eps rows {int(eps.shape[0])} / z rows {int(z.shape[0])} vs context rows {self.rows}")

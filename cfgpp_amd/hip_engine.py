@@ -87,6 +87,11 @@ class HipEngine:
         if self._eps is None or int(self._eps.shape[0]) != 2 * B:      # kept across calls: a captured graph holds its address
             self._eps = torch.empty((2 * B, self.cfg.out_channels, self.H, self.W), dtype=torch.float16, device=self.device)
 
+    def image_condition(self, cond: torch.Tensor):
+        """inpaint UNets: the step-invariant [mask, masked-image latent] channels, [1 or B, in - out, H, W]
+        (include/cfgpp.h: cfgpp_unet_image_condition).  Once per job, before predict / ddim_loop_graph."""
+        self.unet.image_condition(cond)
+
     def predict(self, z: torch.Tensor, t: float):
         """(eps_uc, eps_c), each [B,4,H,W] fp16 - replaces predict_noise's UNet call + chunk(2)."""
         eps = self.unet.forward(z, float(t), self._eps)
@@ -134,6 +139,7 @@ class HipEngine:
 
     # -- fused sampler arithmetic ---------------------------------------------------
     step_ddim = staticmethod(E.step_ddim)
+    step_ddim_masked = staticmethod(E.step_ddim_masked)
     kdiff_input = staticmethod(E.kdiff_input)
     step_kdiff = staticmethod(E.step_kdiff)
     kdiff_denoise = staticmethod(E.kdiff_denoise)

@@ -186,7 +186,7 @@ class StableDiffusion:
         elif method == "npi":
             z = self.inversion(self.encode(src_img.to(self.dtype)), kwargs.get("c"), kwargs.get("c"), cfg_guidance=1.0)
         elif method in ("random", "random_kdiffusion"):
-            size = tuple(kwargs.get("latent_dim", (1, self.cfg.in_channels) + self.latent_hw))
+            size = tuple(kwargs.get("latent_dim", (1, self.cfg.out_channels) + self.latent_hw))
             z = self._randn(size, kwargs.get("seeds"))
             if method == "random_kdiffusion":
                 sigmas = kwargs.get("sigmas", [14.6146])
@@ -322,7 +322,7 @@ class StableDiffusion:
         (latent_diffusion.py:302-346, 454-503, 682-723, 830-879)."""
         B = self._batch_of(c, None)
         sigmas = self.tables.karras_sigmas()
-        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.in_channels) + self.latent_hw,
+        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.out_channels) + self.latent_hw,
                                    sigmas=sigmas, seeds=seeds).to(torch.float16).contiguous()
         xc = torch.empty_like(x)
         den = torch.empty_like(x)
@@ -351,7 +351,7 @@ class StableDiffusion:
         B = self._batch_of(c, None)
         lam = cfg_guidance
         sigmas = self.tables.karras_sigmas()
-        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.in_channels) + self.latent_hw,
+        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.out_channels) + self.latent_hw,
                                    sigmas=sigmas, seeds=seeds).to(torch.float16).contiguous()
         xc, den, uden = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         x2, den2, uden2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
@@ -414,7 +414,7 @@ class BaseDDIM(StableDiffusion):
         B = int(c.shape[0])
         zt = kwargs.get("latents")
         if zt is None:
-            zt = self.initialize_latent(latent_dim=(B, self.cfg.in_channels) + self.latent_hw, seeds=kwargs.get("seeds"))
+            zt = self.initialize_latent(latent_dim=(B, self.cfg.out_channels) + self.latent_hw, seeds=kwargs.get("seeds"))
         z0t, zt = self._ddim_forward(zt.to(self.work_device), uc, c, cfg_guidance, self.cfgpp, callback_fn)
         if kwargs.get("return_latents"):
             return z0t, zt

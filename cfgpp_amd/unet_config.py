@@ -11,7 +11,7 @@ SDXL tables sum to the published 859.5 M / 2567.5 M parameters
 from __future__ import annotations
 
 from collections import OrderedDict
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Tuple
 
 
@@ -54,7 +54,15 @@ TINY_XL = UNetConfig(name="tiny_xl", block_out_channels=(64, 128), level_has_att
                      addition_embed=1, addition_time_embed_dim=32, addition_pooled_dim=64, sample_size=16,
                      vae_scale=0.13025)
 
-CONFIGS = {c.name: c for c in (SD15, SDXL, TINY_SD, TINY_XL)}
+# inpaint UNets (runwayml/stable-diffusion-inpainting, diffusers/stable-diffusion-xl-1.0-inpainting-0.1): conv_in takes
+# 9 channels - the latent (4), the mask (1) and the masked image's latent (4), in diffusers' torch.cat order
+SD15_INPAINT = replace(SD15, name="sd15_inpaint", in_channels=9)
+SDXL_INPAINT = replace(SDXL, name="sdxl_inpaint", in_channels=9)
+TINY_SD_INPAINT = replace(TINY_SD, name="tiny_sd_inpaint", in_channels=9)
+TINY_XL_INPAINT = replace(TINY_XL, name="tiny_xl_inpaint", in_channels=9)
+
+CONFIGS = {c.name: c for c in (SD15, SDXL, TINY_SD, TINY_XL, SD15_INPAINT, SDXL_INPAINT, TINY_SD_INPAINT, TINY_XL_INPAINT)}
+INPAINT_OF = {"sd15": SD15_INPAINT, "sdxl": SDXL_INPAINT, "tiny_sd": TINY_SD_INPAINT, "tiny_xl": TINY_XL_INPAINT}
 
 
 def param_shapes(cfg: UNetConfig) -> "OrderedDict[str, tuple]":

@@ -64,6 +64,19 @@ int cfgpp_step_ddim_h(void* z, void* z0t_out, const void* eps_uc, const void* ep
                       float lam, float c1, float c2, float c3, float c4,
                       int tweedie_uc, int renoise_uc, long n, void* stream);
 
+/* Inpainting with an ordinary (4-channel) UNet: the fp32-latent / fp16-eps update of cfgpp_step_ddim (eps_is_half = 1) on
+ * B x 4 x hw elements, blended in the same pass with the forward-noised source latent (diffusers
+ * StableDiffusionInpaintPipeline.__call__, `num_channels_unet == 4` branch: init_latents_proper =
+ * scheduler.add_noise(image_latents, noise, t_next); latents = (1 - init_mask) * init_latents_proper + init_mask * latents):
+ *     z = mask ? z_new : a*src + b*noise          z0t_out = mask ? z0t : src
+ * mask: uint8 [B][hw], 0 = keep, nonzero = repaint (binarized by the caller); src fp16 [B][4][hw]; noise fp32 [B][4][hw];
+ * (a, b) = (sqrt(at_prev), sqrt(1 - at_prev)) of the step, (1, 0) on the last one.  The two products and the sum are
+ * rounded separately (torch's `a*src.float() + b*noise`).  hw must be a multiple of 4.  An all-ones mask gives the bits
+ * of cfgpp_step_ddim. */
+int cfgpp_step_ddim_masked(void* z, void* z0t_out, const void* eps_uc, const void* eps_c, float lam, float c1, float c2,
+                           float c3, float c4, int tweedie_uc, int renoise_uc, const void* mask, const void* src,
+                           const void* noise, float a, float b, int B, long hw, void* stream);
+
 /* k-diffusion UNet input scaling on fp16 latents: mode 0: xc = x / s
  * (latent_diffusion.py:229-230, s = sqrt(sigma^2+1)); mode 1: xc = x * s (latent_sdxl.py:901). */
 int cfgpp_kdiff_input(const void* x, void* xc, float s, int mode, long n, void* stream);
@@ -131,9 +144,19 @@ int cfgpp_unet_finalize(cfgpp_unet* u);
 int cfgpp_unet_set_context(cfgpp_unet* u, const void* ehs, int rows, int tokens,
                            const void* text_embeds, const void* time_ids, int cond_rows, void* stream);
 
-/* eps[rows][out_ch][H][W] (fp16) = UNet(z[(row % z_rows)], t).  z: [z_rows][in_ch][H][W],
- * fp32 (z_is_half=0) or fp16.  rows = 2*z_rows reproduces cat([zt]*2) / chunk(2) of
- * latent_diffusion.py:153-156: eps_uc = eps[0:z_rows], eps_c = eps[z_rows:]. */
+/* Inpaint UNets (in_channels > out_channels, e.g. SD1.5 / SDXL inpainting: 9 = 4 latent + 1 mask + 4 masked-image latent):
+ * the step-invariant extra input channels, replacing the per-step
+ *     latent_model_input = torch.cat([latent_model_input, mask, masked_image_latents], dim=1)
+ * of diffusers StableDiffusionInpaintPipeline.__call__ / StableDiffusionXLInpaintPipeline.__call__.
+ * cond: fp16 [cond_rows][in_ch - out_ch][H][W] (DEVICE), copied on `stream` into an engine-owned buffer whose address never
+ * changes (a captured cfgpp_sample_graph_ddim graph stays valid when the condition changes).  Row r of the UNet batch reads
+ * condition row (r % z_rows) % cond_rows: cond_rows must be z_rows or 1.  Error on an engine with in_ch == out_ch; a forward
+ * of an inpaint engine before this call is an error. */
+int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, void* stream);
+
+/* eps[rows][out_ch][H][W] (fp16) = UNet(z[(row % z_rows)], t).  z: [z_rows][out_ch][H][W] (the latent channels; an inpaint
+ * UNet takes the rest from cfgpp_unet_image_condition), fp32 (z_is_half=0) or fp16.  rows = 2*z_rows reproduces
+ * cat([zt]*2) / chunk(2) of latent_diffusion.py:153-156: eps_uc = eps[0:z_rows], eps_c = eps[z_rows:]. */
 int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, float t,
                        void* eps_out, int rows, void* stream);
 
@@ -143,7 +166,7 @@ int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
  * host_steps[n_steps][5] = {t, c1, c2, c3, c4} per step: exactly the values the eager loop would pass to
  * cfgpp_unet_forward and cfgpp_step_ddim (HOST memory, copied before the call returns); they live in a device table
  * indexed by a device step counter, so one graph serves every step and every later call with the same buffers (the
- * engine keeps the most recent graph; other buffers / flags / batch re-capture).  z, z0t: [z_rows][in_ch][H][W] fp32 or
+ * engine keeps the most recent graph; other buffers / flags / batch re-capture).  z, z0t: [z_rows][out_ch][H][W] fp32 or
  * fp16 (z updated in place, z0t written every step); eps: [rows][out_ch][H][W] fp16 scratch for the UNet output;
  * eps_uc / eps_c point into it (the same pointer for the lambda == 1 Lightning form).  The first call at a batch runs one
  * eager forward (tile tuning, see above) and captures on an engine-owned stream - `stream` may be the legacy default
