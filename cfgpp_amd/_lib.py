@@ -59,6 +59,7 @@ PROTOTYPES = {
     "cfgpp_sample_graph_ddim": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _I, C.POINTER(C.c_float), _I, _F, _I, _I, _P]),
     "cfgpp_unet_profile": (_I, [_P, _P, _I, _I, _F, _P, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p, _L]),
     "cfgpp_unet_tuning": (_I, [_P, _I, C.POINTER(C.c_int), _I, _I]),
+    "cfgpp_unet_attach_control": (_I, [_P, _P, _F]),
     "cfgpp_unet_flops": (C.c_double, [_P, _I]),
     "cfgpp_unet_device_bytes": (C.c_double, [_P]),
     "cfgpp_vae_create": (_P, [_I, _I, _I, _F, _I]),
@@ -95,6 +96,11 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_conv_in_add": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_cn_conv3x3": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_residual_add": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), _I, _I, _F, _P]),
+    "cfgpp_op_residual_nchw": (_I, [_P, _P, _I, _I, _I, _I, _F, _P]),
+    "cfgpp_controlnet_residual": (_I, [_P, _I, _F, _P, _I, C.POINTER(C.c_int), _P]),
     "cfgpp_op_vae_posterior": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "cfgpp_op_conv_out": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_out_ex": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

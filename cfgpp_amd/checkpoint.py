@@ -120,3 +120,58 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
         if t1 is not None:
             kw["text_encoder"] = t1
     return kw, missing
+
+
+def controlnet_config_from_json(conf: dict, base):
+    """the ``UNetConfig`` of a diffusers ``ControlNetModel`` config.json (its UNet-shaped fields), starting from the solver's
+    UNet config ``base``.  Refuses what the engine does not build, naming the field."""
+    from dataclasses import replace
+    from .controlnet import EMBED_CHANNELS
+    if conf.get("global_pool_conditions"):
+        raise CfgppError("controlnet config.json: global_pool_conditions=true (a pooled 'shuffle'-style ControlNet) is not supported")
+    if str(conf.get("controlnet_conditioning_channel_order", "rgb")).lower() != "rgb":
+        raise CfgppError(f"controlnet config.json: controlnet_conditioning_channel_order={conf['controlnet_conditioning_channel_order']!r} "
+                         "is not supported (rgb only)")
+    emb = tuple(conf.get("conditioning_embedding_out_channels", EMBED_CHANNELS))
+    if emb != EMBED_CHANNELS:
+        raise CfgppError(f"controlnet config.json: conditioning_embedding_out_channels={list(emb)} is not supported "
+                         f"(the engine builds {list(EMBED_CHANNELS)})")
+    if int(conf.get("conditioning_channels", 3)) != 3:
+        raise CfgppError(f"controlnet config.json: conditioning_channels={conf['conditioning_channels']} is not supported (3)")
+    boc = tuple(int(c) for c in conf.get("block_out_channels", base.block_out_channels))
+    L = len(boc)
+
+    def per_level(v, default):
+        if v is None:
+            return tuple(default)
+        return tuple(int(x) for x in v) if isinstance(v, (list, tuple)) else (int(v),) * L
+
+    types_ = conf.get("down_block_types")
+    attn = tuple(int("CrossAttn" in t) for t in types_) if types_ else tuple(base.level_has_attn)
+    depth = per_level(conf.get("transformer_layers_per_block"), base.transformer_depth)
+    heads = per_level(conf.get("num_attention_heads") or conf.get("attention_head_dim"), base.num_heads)   # diffusers' naming quirk
+    add = 1 if conf.get("addition_embed_type") == "text_time" else 0
+    tdim = int(conf.get("addition_time_embed_dim") or base.addition_time_embed_dim)
+    pooled = int(conf["projection_class_embeddings_input_dim"]) - 6 * tdim if add and conf.get("projection_class_embeddings_input_dim") \
+        else base.addition_pooled_dim
+    return replace(base, name=base.name + "_controlnet", in_channels=int(conf.get("in_channels", base.out_channels)),
+                   out_channels=base.out_channels, block_out_channels=boc, layers_per_block=int(conf.get("layers_per_block", base.layers_per_block)),
+                   level_has_attn=attn, transformer_depth=depth, num_heads=heads,
+                   cross_attention_dim=int(conf.get("cross_attention_dim", base.cross_attention_dim)), addition_embed=add,
+                   addition_time_embed_dim=tdim, addition_pooled_dim=pooled, norm_groups=int(conf.get("norm_num_groups", base.norm_groups)))
+
+
+def controlnet_from_dir(path, base):
+    """a diffusers ``controlnet/`` folder (config.json + diffusion_pytorch_model[.fp16].safetensors), or a safetensors file
+    (with a config.json next to it, or the solver's UNet config) -> (UNetConfig, state-dict items)"""
+    import json
+    from .weights import load_safetensors_iter
+    folder, weights = (path, _weights_in(path)) if os.path.isdir(path) else (os.path.dirname(path), path)
+    if not weights or not os.path.exists(weights):
+        raise CfgppError(f"controlnet: no diffusion_pytorch_model[.fp16].safetensors in {path}")
+    conf_path = os.path.join(folder, "config.json")
+    cfg = base
+    if os.path.exists(conf_path):
+        with open(conf_path) as f:
+            cfg = controlnet_config_from_json(json.load(f), base)
+    return cfg, load_safetensors_iter(weights)

@@ -63,6 +63,29 @@ int cfgpp_op_conv_in(const void* z, int z_is_half, void* out, const float* w, co
  * cond = NULL is cfgpp_op_conv_in. */
 int cfgpp_op_conv_in_cond(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, void* out, const float* w,
                           const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream);
+/* conv_in_cond plus an fp16 addend in the output's layout [add_rows][H+2][W+2][Cout] (row (r % zB) % add_rows), added to the
+ * fp16-rounded conv result and rounded again: the ControlNet's `sample = conv_in(sample) + controlnet_cond` (diffusers
+ * ControlNetModel.forward).  addend = NULL is cfgpp_op_conv_in_cond bit for bit. */
+int cfgpp_op_conv_in_add(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, const void* addend, int add_rows,
+                         void* out, const float* w, const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream);
+/* ControlNet conditioning-embedding convolution (diffusers ControlNetConditioningEmbedding conv_in / blocks.N): 3x3, pad 1,
+ * stride 1 or 2, Ci, Co <= 256, w [9][Ci][Co] fp32 (tap-major), fp32 accumulation, fp16 output, silu = 1: F.silu after the fp16
+ * rounding (rounded again).  in_kind 0: dense NHWC fp16 [R][Hi][Wi][Ci]; 1 / 2: NCHW fp16 / fp32 [R][Ci][Hi][Wi].  out_pad 0: dense
+ * NHWC fp16 [R][Ho][Wo][Co]; 1: halo-padded NHWC [R][Ho+2][Wo+2][Co] (interior written).  Ho = (Hi - 1) / stride + 1. */
+int cfgpp_op_cn_conv3x3(const void* in, int in_kind, void* out, int out_pad, const float* w, const float* bias, int R, int Ci, int Co,
+                        int Hi, int Wi, int stride, int silu, void* stream);
+/* the ControlNet residual add of the controlled UNet on n <= 32 tensor pairs in one launch: dst[i] = half(float(dst[i]) +
+ * float(half(float(src[i]) * scale))) - torch's fp16 `s + r * scale` - over the interior of halo-padded NHWC fp16 tensors,
+ * hwc[3 * i ..] = {H, W, C} of pair i (C % 8 == 0), `rows` rows.  dst / src: HOST arrays of device pointers (the table is
+ * uploaded synchronously: test hook). */
+int cfgpp_op_residual_add(void* const* dst, const void* const* src, const int* hwc, int n, int rows, float scale, void* stream);
+/* halo-padded NHWC fp16 [rows][H+2][W+2][C] -> dense fp32 NCHW, each value multiplied by scale and rounded to fp16 first */
+int cfgpp_op_residual_nchw(const void* src, float* out, int rows, int H, int W, int C, float scale, void* stream);
+/* ControlNet test hook: residual i (0 .. n_down - 1 the down-block residuals in diffusers' order, n_down the mid-block
+ * residual) of the last ControlNet forward, multiplied by `scale` and rounded to fp16 as the controlled UNet adds it, into a
+ * dense fp32 NCHW buffer out [rows][C][H][W].  Returns the number of residuals when out is NULL. */
+int cfgpp_controlnet_residual(cfgpp_unet* cn, int i, float scale, float* out, int rows, int* hwc_out, void* stream);
+
 /* quant_conv (1x1, 8->8) + DiagonalGaussian posterior on the encoder's 8-channel conv_out (fp32 NCHW). */
 int cfgpp_op_vae_posterior(const float* conv_out, const float* qw, const float* qb, const float* noise, float* z,
                            float* moments, int B, int HW, float scale, void* stream);

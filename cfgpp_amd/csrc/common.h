@@ -38,6 +38,15 @@ int step_advance_launch(const float* tab, int* idx, float* cur, hipStream_t s);
 int step_ddim_dev_launch(void* z, void* z0t_out, const void* eps_uc, const void* eps_c, int eps_is_half, int z_is_half, float lam,
                          const float* cdev, int tweedie_uc, int renoise_uc, long n, hipStream_t s);
 
+// ControlNet residual add (controlnet_kernels.hip; used by unet.hip): one entry per skip connection / the mid-block output,
+// both tensors halo-padded NHWC fp16 of the same H / W / C
+struct CnAddEntry {
+    half_t* dst;
+    const half_t* src;
+    int H, W, C, pad_;
+};
+int cn_residual_add_launch(const CnAddEntry* tab, int n, long max_n8, int rows, float scale, hipStream_t s);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- activation layouts -----------------------------------------------------

@@ -15,6 +15,8 @@ namespace {
 // of an inpaint UNet (mask + masked-image latent), row (r % zB) % cond_rows: diffusers'
 // torch.cat([latent_model_input, mask, masked_image_latents], dim=1) is an index computation as well.
 // cond == null: Cc = 0 and the arithmetic is the plain 4-channel (or VAE) conv_in's.
+// add (ControlNet): fp16 addend in the output's layout [add_rows][H+2][W+2][Cout], row (r % zB) % add_rows, added to the
+// fp16-rounded conv result and rounded again - diffusers' `sample + controlnet_cond` on fp16 tensors.  null: today's bits.
 // w: [9*Cin][Cout] fp32 (k = tap*Cin + ci, Cin = Cz + Cc), bias [Cout] fp32.
 // ---------------------------------------------------------------------------
 template <typename TIN>
@@ -22,7 +24,8 @@ __global__ void __launch_bounds__(256)
 conv_in_kernel(const TIN* __restrict__ z, const half_t* __restrict__ cond, int Cc, int cond_rows,
                half_t* __restrict__ out, const float* __restrict__ w,
                const float* __restrict__ bias, int R, int zB, int Cz, int H, int W, int Cout,
-               const float* __restrict__ pre_w, const float* __restrict__ pre_b, float in_scale) {
+               const float* __restrict__ pre_w, const float* __restrict__ pre_b, float in_scale,
+               const half_t* __restrict__ add, int add_rows) {
     constexpr int TP = 16;                 // pixels per block
     __shared__ float patch[TP][9 * 16];
     const int r = blockIdx.y;
@@ -73,7 +76,9 @@ conv_in_kernel(const TIN* __restrict__ z, const half_t* __restrict__ cond, int C
             const int p = p0 + tp;
             if (p < HW) {
                 const int y = p / W, x = p - y * W;
-                out[((long)(r * (H + 2) + y + 1) * (W + 2) + x + 1) * Cout + co] = (half_t)acc[tp];
+                half_t v = (half_t)acc[tp];
+                if (add) v = (half_t)((float)v + (float)add[((long)((zb % add_rows) * (H + 2) + y + 1) * (W + 2) + x + 1) * Cout + co]);
+                out[((long)(r * (H + 2) + y + 1) * (W + 2) + x + 1) * Cout + co] = v;
             }
         }
     }
@@ -340,9 +345,20 @@ int cfgpp_op_vae_posterior(const float* conv_out, const float* qw, const float* 
 }
 
 // z: the first Cz input channels; cond (fp16 [cond_rows][Cc][H][W]) or null: the last Cc (inpaint UNets)
+int cfgpp_op_conv_in_add(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, const void* addend, int add_rows,
+                         void* out, const float* w, const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream);
+
 int cfgpp_op_conv_in_cond(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, void* out, const float* w,
                           const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream) {
+    return cfgpp_op_conv_in_add(z, z_is_half, cond, cond_rows, Cc, nullptr, 1, out, w, bias, R, zB, Cz, H, W, Cout, stream);
+}
+
+int cfgpp_op_conv_in_add(const void* z, int z_is_half, const void* cond, int cond_rows, int Cc, const void* addend, int add_rows,
+                         void* out, const float* w, const float* bias, int R, int zB, int Cz, int H, int W, int Cout, void* stream) {
     CFGPP_REQUIRE(Cz >= 1 && Cz <= 8, "conv_in: Cin=%d (<= 8)", Cz);
+    CFGPP_REQUIRE(!addend || add_rows > 0, "conv_in: addend with add_rows=%d", add_rows);
+    const half_t* add = (const half_t*)addend;
+    if (!add) add_rows = 1;
     CFGPP_REQUIRE(!cond || (Cc >= 1 && Cz + Cc <= 16 && cond_rows > 0), "conv_in: condition of %d channels x %d rows on %d latent channels (Cin <= 16)",
                   Cc, cond_rows, Cz);
     CFGPP_REQUIRE(z && out && w && R > 0 && zB > 0, "conv_in: bad args");
@@ -351,10 +367,10 @@ int cfgpp_op_conv_in_cond(const void* z, int z_is_half, const void* cond, int co
     hipStream_t s = (hipStream_t)stream;
     if (z_is_half)
         hipLaunchKernelGGL(conv_in_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)z, (const half_t*)cond, Cc, cond_rows, (half_t*)out, w, bias,
-                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f);
+                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f, add, add_rows);
     else
         hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (const half_t*)cond, Cc, cond_rows, (half_t*)out, w, bias,
-                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f);
+                           R, zB, Cz, H, W, Cout, (const float*)nullptr, (const float*)nullptr, 1.0f, add, add_rows);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -368,10 +384,10 @@ int cfgpp_op_conv_in_ex(const void* z, int z_is_half, void* out, const float* w,
     hipStream_t s = (hipStream_t)stream;
     if (z_is_half)
         hipLaunchKernelGGL(conv_in_kernel<half_t>, grid, dim3(256), 0, s, (const half_t*)z, (const half_t*)nullptr, 0, 1, (half_t*)out, w, bias,
-                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
+                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale, (const half_t*)nullptr, 1);
     else
         hipLaunchKernelGGL(conv_in_kernel<float>, grid, dim3(256), 0, s, (const float*)z, (const half_t*)nullptr, 0, 1, (half_t*)out, w, bias,
-                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale);
+                           R, zB, Cin, H, W, Cout, pre_w, pre_b, in_scale, (const half_t*)nullptr, 1);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }

@@ -50,6 +50,18 @@ struct cfgpp_unet : EngineBase {
     half_t *hq[4] = {nullptr, nullptr, nullptr, nullptr}, *hk[4] = {nullptr, nullptr, nullptr, nullptr},
            *hvt[4] = {nullptr, nullptr, nullptr, nullptr};
 
+    // ---- ControlNet.  control = this engine IS a ControlNet (cfgpp_unet_create with out_channels = 0): conv_in adds the embedded control image,
+    // the plan ends with the zero convolutions into the persistent residuals ctrl_res (the skips' order, then the mid block's)
+    bool control = false;
+    std::vector<int> embed_ch;              // ControlNetConditioningEmbedding block_out_channels
+    std::vector<Op> img_plan;               // the embedding (cfgpp_unet_image_condition), rows = image rows
+    const void* img_in = nullptr; int img_in_half = 0;
+    half_t* d_img_emb = nullptr; int img_rows = 0;      // embedded image: halo-padded NHWC [max_rows][H+2][W+2][c0], fixed address
+    std::vector<Tensor> ctrl_res;
+    // controlled UNet: the tensors the residuals are added to (skips, then the mid-block output), the attached net and its scale
+    std::vector<Tensor> ctrl_dst;
+    cfgpp_unet* ctrl = nullptr; float ctrl_scale = 0.f;
+    CnAddEntry* d_ctrl_tab = nullptr; long ctrl_max_n8 = 0;
 };
 
 namespace {
@@ -82,6 +94,27 @@ void build_param_table(cfgpp_unet* u) {
     expect_resnet(u, "mid_block.resnets.0", cm, cm, temb);
     expect_transformer(u, "mid_block.attentions.0", cm, c.transformer_depth[L - 1], c.cross_attention_dim);
     expect_resnet(u, "mid_block.resnets.1", cm, cm, temb);
+    if (u->control) {
+        // ControlNetConditioningEmbedding: conv_in, then per level a stride-1 and a stride-2 conv, conv_out to c0
+        const std::vector<int>& e = u->embed_ch;
+        const std::string q = "controlnet_cond_embedding.";
+        expect_conv(u, q + "conv_in", e[0], 3, 3);
+        for (size_t i = 0; i + 1 < e.size(); ++i) {
+            expect_conv(u, q + "blocks." + std::to_string(2 * i), e[i], e[i], 3);
+            expect_conv(u, q + "blocks." + std::to_string(2 * i + 1), e[i + 1], e[i], 3);
+        }
+        expect_conv(u, q + "conv_out", c0, e.back(), 3);
+        // zero convolutions: one per skip connection (conv_in, every down resnet / attention, every downsampler), then the mid block
+        int k = 0;
+        expect_conv(u, "controlnet_down_blocks." + std::to_string(k++), c0, c0, 1);
+        for (int i = 0; i < L; ++i) {
+            const long co = c.block_out_channels[i];
+            for (int j = 0; j < c.layers_per_block; ++j) expect_conv(u, "controlnet_down_blocks." + std::to_string(k++), co, co, 1);
+            if (i != L - 1) expect_conv(u, "controlnet_down_blocks." + std::to_string(k++), co, co, 1);
+        }
+        expect_conv(u, "controlnet_mid_block", cm, cm, 1);
+        return;                              // no up path, no conv_out
+    }
     // up blocks (diffusers: reversed channels; layers_per_block+1 resnets each)
     long prev = cm;
     for (int i = 0; i < L; ++i) {
@@ -113,12 +146,89 @@ struct ResW {
     int cin, cout;
 };
 
+// ControlNet tail of the plan (control mode): the 1x1 zero convolutions of every skip and of the mid-block output into persistent
+// residual tensors (the controlled UNet's skip layout, so the add is elementwise), and the embedding plan of the control image
+// (ControlNetConditioningEmbedding: SiLU after every conv but conv_out), whose output is conv_in's addend.
+int controlnet_tail(cfgpp_unet* u, Builder& B, Plan& P, const std::vector<Tensor>& skips, const Tensor& mid) {
+    const cfgpp_unet_config& c = u->cfg;
+    const int R = c.max_rows, c0 = c.block_out_channels[0];
+    auto persist = [&](int H, int W, int C) {
+        Tensor t; t.H = H; t.W = W; t.C = C;
+        t.p = (half_t*)u->dmalloc((size_t)R * (H + 2) * (W + 2) * C * sizeof(half_t));      // zeroed: the halo stays zero
+        return t;
+    };
+    for (size_t k = 0; k <= skips.size(); ++k) {
+        const Tensor& src = k < skips.size() ? skips[k] : mid;
+        const std::string key = k < skips.size() ? "controlnet_down_blocks." + std::to_string(k) : std::string("controlnet_mid_block");
+        half_t* w = B.linear(key + ".weight"); float* b = B.f32(key + ".bias");
+        Tensor r = persist(src.H, src.W, src.C);
+        CFGPP_REQUIRE(r.p, "finalize: hipMalloc failed");
+        P.conv1x1(src, nullptr, r, w, b);
+        u->ctrl_res.push_back(r);
+    }
+    // ---- embedding: direct convolutions at the image size, then conv_out on the implicit GEMM ----
+    const std::vector<int>& e = u->embed_ch;
+    const int n = (int)e.size();
+    const std::string q = "controlnet_cond_embedding.";
+    struct Layer { std::string key; int ci, co, stride; };
+    std::vector<Layer> layers;
+    layers.push_back({q + "conv_in", 3, e[0], 1});
+    for (int i = 0; i + 1 < n; ++i) {
+        layers.push_back({q + "blocks." + std::to_string(2 * i), e[i], e[i], 1});
+        layers.push_back({q + "blocks." + std::to_string(2 * i + 1), e[i], e[i + 1], 2});
+    }
+    // dense NHWC ping-pong scratch for every layer but the last direct one, which writes conv_out's halo-padded input
+    long scratch = 1;
+    {
+        int h = c.sample_h << (n - 1), w = c.sample_w << (n - 1);
+        for (size_t l = 0; l + 1 < layers.size(); ++l) {
+            if (layers[l].stride == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+            scratch = std::max(scratch, (long)R * h * w * layers[l].co);
+        }
+    }
+    half_t* buf[2] = {(half_t*)u->dmalloc((size_t)scratch * sizeof(half_t), false), (half_t*)u->dmalloc((size_t)scratch * sizeof(half_t), false)};
+    Tensor pre = persist(c.sample_h, c.sample_w, e.back());
+    CFGPP_REQUIRE(buf[0] && buf[1] && pre.p, "finalize: hipMalloc failed");
+    cfgpp_unet* uu = u;
+    int h = c.sample_h << (n - 1), w = c.sample_w << (n - 1);
+    for (size_t l = 0; l < layers.size(); ++l) {
+        const Layer& ly = layers[l];
+        HostParam* pw = B.get(ly.key + ".weight");
+        CFGPP_REQUIRE(pw, "finalize: %s", B.err.c_str());
+        std::vector<float> r((size_t)9 * ly.ci * ly.co);          // OIHW -> [tap][ci][co]
+        for (int o = 0; o < ly.co; ++o) for (int i = 0; i < ly.ci; ++i) for (int t = 0; t < 9; ++t)
+            r[((size_t)t * ly.ci + i) * ly.co + o] = (float)pw->h[((size_t)o * ly.ci + i) * 9 + t];
+        B.drop(ly.key + ".weight");
+        float* dw = B.upload(r); float* db = B.f32(ly.key + ".bias");
+        const bool last = l + 1 == layers.size();
+        const half_t* in = l == 0 ? nullptr : buf[(l - 1) & 1];
+        half_t* out = last ? pre.p : buf[l & 1];
+        const int hi = h, wi = w, ci = ly.ci, co = ly.co, st = ly.stride, first = l == 0;
+        u->img_plan.push_back([=](hipStream_t s, int rows) {
+            return cfgpp_op_cn_conv3x3(first ? uu->img_in : in, first ? (uu->img_in_half ? 1 : 2) : 0, out, last ? 1 : 0, dw, db, rows, ci,
+                                       co, hi, wi, st, 1, s);
+        });
+        if (st == 2) { h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1; }
+    }
+    CFGPP_REQUIRE(h == c.sample_h && w == c.sample_w, "finalize: internal error, the embedding ends at %d x %d", h, w);
+    {
+        half_t* wo = B.conv3(q + "conv_out.weight"); float* bo = B.f32(q + "conv_out.bias");
+        Tensor dst; dst.p = u->d_img_emb; dst.H = c.sample_h; dst.W = c.sample_w; dst.C = c0;
+        Plan PI{u, &B, &u->img_plan};
+        const double macs = u->macs_per_row;
+        PI.conv3x3(pre, dst, wo, bo, 1, nullptr, 0, nullptr);
+        u->macs_per_row = macs;               // once per job: not part of a forward's FLOPs
+    }
+    CFGPP_REQUIRE(B.ok, "finalize: %s", B.err.c_str());
+    return 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
 extern "C" {
 
-cfgpp_unet* cfgpp_unet_create(const cfgpp_unet_config* cfg, int device_id) {
+static cfgpp_unet* unet_new(const cfgpp_unet_config* cfg, int device_id, const int* embed, int n_embed) {
     if (!cfg) { cfgpp_set_error("unet_create: null config"); return nullptr; }
     if (cfg->num_levels < 1 || cfg->num_levels > 4 || cfg->layers_per_block < 1 || cfg->max_rows < 1) {
         cfgpp_set_error("unet_create: bad config"); return nullptr;
@@ -132,7 +242,7 @@ cfgpp_unet* cfgpp_unet_create(const cfgpp_unet_config* cfg, int device_id) {
         }
     }
     if (cfg->cross_attention_dim % 64 != 0) { cfgpp_set_error("unet_create: cross_attention_dim must be a multiple of 64"); return nullptr; }
-    if (cfg->in_channels > cfg->out_channels && cfg->in_channels > 16) {
+    if (!embed && cfg->in_channels > cfg->out_channels && cfg->in_channels > 16) {
         cfgpp_set_error("unet_create: in_channels=%d out_channels=%d (an inpaint UNet takes at most 16 input channels)", cfg->in_channels,
                         cfg->out_channels);
         return nullptr;
@@ -149,9 +259,24 @@ cfgpp_unet* cfgpp_unet_create(const cfgpp_unet_config* cfg, int device_id) {
     if (hipSetDevice(device_id) != hipSuccess) { cfgpp_set_error("unet_create: hipSetDevice failed"); return nullptr; }
     cfgpp_unet* u = new cfgpp_unet();
     u->cfg = *cfg; u->device = device_id; u->max_rows = cfg->max_rows; u->norm_groups = cfg->norm_groups;
+    if (embed) { u->control = true; u->embed_ch.assign(embed, embed + n_embed); }
     build_param_table(u);
     return u;
 }
+
+cfgpp_unet* cfgpp_unet_create(const cfgpp_unet_config* cfg, int device_id) {
+    if (cfg && cfg->out_channels == 0) {
+        // a ControlNet: diffusers' ControlNetConditioningEmbedding with its default conditioning_embedding_out_channels
+        static const int embed[4] = {16, 32, 96, 256};
+        if (cfg->in_channels < 1 || cfg->in_channels > 8) {
+            cfgpp_set_error("unet_create: ControlNet (out_channels = 0) with in_channels=%d (1 .. 8 latent channels)", cfg->in_channels);
+            return nullptr;
+        }
+        return unet_new(cfg, device_id, embed, 4);
+    }
+    return unet_new(cfg, device_id, nullptr, 0);
+}
+
 
 void cfgpp_unet_destroy(cfgpp_unet* u) {
     if (!u) return;
@@ -237,7 +362,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         for (int i = 0; i < L; ++i)
             for (int j = 0; j < c.layers_per_block; ++j) res_names.push_back("down_blocks." + std::to_string(i) + ".resnets." + std::to_string(j));
         res_names.push_back("mid_block.resnets.0"); res_names.push_back("mid_block.resnets.1");
-        for (int i = 0; i < L; ++i)
+        for (int i = 0; i < L && !u->control; ++i)
             for (int j = 0; j < c.layers_per_block + 1; ++j) res_names.push_back("up_blocks." + std::to_string(i) + ".resnets." + std::to_string(j));
     }
     std::map<std::string, int> temb_off;
@@ -417,7 +542,14 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
             r[(size_t)(t * Ci + i) * c0 + o] = pw->f[((size_t)o * Ci + i) * 9 + t];
         float* dw = B.upload(r); float* db = B.upload(pb->f);
         cfgpp_unet* uu = u; half_t* xp = x.p; const int HH = H, WW = W;
-        if (Ci > c.out_channels) {          // inpaint UNet: latent channels from z, the rest from the condition buffer
+        if (u->control) {                   // ControlNet: conv_in(z) + the embedded control image (fp16 sum)
+            u->d_img_emb = (half_t*)u->dmalloc((size_t)R * (H + 2) * (W + 2) * c0 * sizeof(half_t));
+            CFGPP_REQUIRE(u->d_img_emb, "finalize: hipMalloc failed");
+            u->plan.push_back([=](hipStream_t s, int rows) {
+                return cfgpp_op_conv_in_add(uu->in_z, uu->in_z_half, nullptr, 1, 0, uu->d_img_emb, uu->img_rows, xp, dw, db, rows,
+                                            uu->in_z_rows, Ci, HH, WW, c0, s);
+            });
+        } else if (Ci > c.out_channels) {          // inpaint UNet: latent channels from z, the rest from the condition buffer
             const int Cz = c.out_channels, Cc = Ci - Cz;
             u->d_cond = (half_t*)u->dmalloc((size_t)R * Cc * H * W * sizeof(half_t));
             CFGPP_REQUIRE(u->d_cond, "finalize: hipMalloc failed");
@@ -461,6 +593,32 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         Tensor w = resblock("mid_block.resnets.1", z, nullptr, cm);
         u->rel(z);
         x = w;
+    }
+    if (u->control) {
+        int e = controlnet_tail(u, B, P, skips, x);
+        if (e) return e;
+        skips.clear();
+        CFGPP_REQUIRE(B.ok, "finalize: %s", B.err.c_str());
+        CFGPP_HIP_CHECK(hipDeviceSynchronize());
+        u->plan_kind.resize(u->plan.size(), 3); u->plan_macs.resize(u->plan.size(), 0.0); u->plan_desc.resize(u->plan.size());
+        u->finalized = true;
+        return 0;
+    }
+    // ---- ControlNet residuals (cfgpp_unet_attach_control): skip_i += down_res[i], mid += mid_res, after the mid block has read
+    // the last skip.  The up path's GroupNorms must not use the statistics the skips' producers wrote: the op clears their flags.
+    {
+        u->ctrl_dst = skips; u->ctrl_dst.push_back(x);
+        u->d_ctrl_tab = (CnAddEntry*)u->dmalloc(u->ctrl_dst.size() * sizeof(CnAddEntry));
+        CFGPP_REQUIRE(u->d_ctrl_tab, "finalize: hipMalloc failed");
+        for (const Tensor& t : u->ctrl_dst) u->ctrl_max_n8 = std::max(u->ctrl_max_n8, (long)R * t.H * t.W * (t.C / 8));
+        cfgpp_unet* uu = u;
+        const int n = (int)u->ctrl_dst.size();
+        u->plan.push_back([uu, n](hipStream_t s, int rows) {
+            if (!uu->ctrl || uu->ctrl_scale == 0.f) return 0;
+            for (const Tensor& t : uu->ctrl_dst) if (t.gst_ok) *t.gst_ok = 0;
+            return cn_residual_add_launch(uu->d_ctrl_tab, n, uu->ctrl_max_n8, rows, uu->ctrl_scale, s);
+        });
+        u->tag(3, 0.0, "controlnet residual add");
     }
     // ---- up ----
     for (int i = 0; i < L; ++i) {
@@ -528,6 +686,15 @@ int cfgpp_unet_set_context(cfgpp_unet* u, const void* ehs, int rows, int tokens,
 
 int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, void* stream) {
     CFGPP_REQUIRE(u && u->finalized, "image_condition: engine not finalized");
+    if (u->control) {           // ControlNet: embed the control image once per job (ControlNetConditioningEmbedding)
+        CFGPP_REQUIRE(cond && cond_rows > 0 && cond_rows <= u->cfg.max_rows, "image_condition: ControlNet image_rows=%d (1 .. %d)", cond_rows,
+                      u->cfg.max_rows);
+        u->img_in = cond; u->img_in_half = 1;
+        for (auto& op : u->img_plan) { int e = op((hipStream_t)stream, cond_rows); if (e) return e; }
+        u->img_in = nullptr;
+        u->img_rows = cond_rows;
+        return 0;
+    }
     CFGPP_REQUIRE(u->cfg.in_channels > u->cfg.out_channels && u->d_cond,
                   "image_condition: this UNet takes %d input channels for %d latent channels - no image condition (not an inpaint UNet)",
                   u->cfg.in_channels, u->cfg.out_channels);
@@ -538,15 +705,69 @@ int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, v
     return 0;
 }
 
+int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale) {
+    CFGPP_REQUIRE(u && u->finalized, "attach_control: UNet not finalized");
+    CFGPP_REQUIRE(!u->control, "attach_control: the target is itself a ControlNet");
+    if (!cn) { u->ctrl = nullptr; u->ctrl_scale = 0.f; return 0; }
+    CFGPP_REQUIRE(cn->finalized && cn->control, "attach_control: not a finalized ControlNet (cfgpp_unet_create with out_channels = 0, then finalize)");
+    const cfgpp_unet_config &a = u->cfg, &b = cn->cfg;
+    CFGPP_REQUIRE(a.num_levels == b.num_levels && a.layers_per_block == b.layers_per_block, "attach_control: levels %d x %d vs the UNet's %d x %d",
+                  b.num_levels, b.layers_per_block, a.num_levels, a.layers_per_block);
+    for (int i = 0; i < a.num_levels; ++i)
+        CFGPP_REQUIRE(a.block_out_channels[i] == b.block_out_channels[i], "attach_control: channels of level %d: %d vs the UNet's %d", i,
+                      b.block_out_channels[i], a.block_out_channels[i]);
+    CFGPP_REQUIRE(a.sample_h == b.sample_h && a.sample_w == b.sample_w, "attach_control: latent %d x %d vs the UNet's %d x %d", b.sample_h,
+                  b.sample_w, a.sample_h, a.sample_w);
+    CFGPP_REQUIRE(a.max_rows == b.max_rows, "attach_control: max_rows %d vs the UNet's %d", b.max_rows, a.max_rows);
+    CFGPP_REQUIRE(b.in_channels == a.out_channels, "attach_control: the ControlNet takes %d latent channels, the UNet %d", b.in_channels,
+                  a.out_channels);
+    CFGPP_REQUIRE(cn->ctrl_res.size() == u->ctrl_dst.size(), "attach_control: %d residuals for %d skip connections + mid block",
+                  (int)cn->ctrl_res.size(), (int)u->ctrl_dst.size());
+    std::vector<CnAddEntry> tab(u->ctrl_dst.size());
+    for (size_t i = 0; i < tab.size(); ++i) {
+        const Tensor &d = u->ctrl_dst[i], &r = cn->ctrl_res[i];
+        CFGPP_REQUIRE(d.H == r.H && d.W == r.W && d.C == r.C, "attach_control: residual %d is %d x %d x %d, the UNet tensor %d x %d x %d", (int)i,
+                      r.H, r.W, r.C, d.H, d.W, d.C);
+        tab[i] = CnAddEntry{d.p, r.p, d.H, d.W, d.C, 0};
+    }
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    CFGPP_HIP_CHECK(hipDeviceSynchronize());         // an earlier forward may still read the table
+    CFGPP_HIP_CHECK(hipMemcpy(u->d_ctrl_tab, tab.data(), tab.size() * sizeof(CnAddEntry), hipMemcpyHostToDevice));
+    u->ctrl = cn; u->ctrl_scale = scale;
+    return 0;
+}
+
+int cfgpp_controlnet_residual(cfgpp_unet* cn, int i, float scale, float* out, int rows, int* hwc_out, void* stream) {
+    CFGPP_REQUIRE(cn && cn->finalized && cn->control, "controlnet_residual: not a finalized ControlNet");
+    const int n = (int)cn->ctrl_res.size();
+    if (!out && !hwc_out) return n;
+    CFGPP_REQUIRE(i >= 0 && i < n, "controlnet_residual: index %d (0 .. %d)", i, n - 1);
+    const Tensor& r = cn->ctrl_res[i];
+    if (hwc_out) { hwc_out[0] = r.H; hwc_out[1] = r.W; hwc_out[2] = r.C; }
+    if (!out) return n;
+    CFGPP_REQUIRE(rows > 0 && rows <= cn->cfg.max_rows, "controlnet_residual: rows=%d", rows);
+    int e = cfgpp_op_residual_nchw(r.p, out, rows, r.H, r.W, r.C, scale, stream);
+    return e ? e : n;
+}
+
 int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, float t, void* eps_out, int rows,
                        void* stream) {
     CFGPP_REQUIRE(u && u->finalized, "forward: context not finalized");
     CFGPP_REQUIRE(u->ctx_set, "forward: set_context has not been called");
     CFGPP_REQUIRE(z && eps_out && z_rows > 0 && rows > 0 && rows <= u->cfg.max_rows, "forward: bad args (rows=%d max=%d)", rows, u->cfg.max_rows);
     CFGPP_REQUIRE(rows == u->ctx_rows, "forward: rows=%d but context was set for %d rows", rows, u->ctx_rows);
-    CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
+    CFGPP_REQUIRE(u->control || u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
                   "forward: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",
                   u->cfg.in_channels, z_rows, u->cond_rows);
+    CFGPP_REQUIRE(!u->control || u->img_rows > 0, "forward: ControlNet without a control image (call cfgpp_unet_image_condition first)");
+    if (u->ctrl && u->ctrl_scale != 0.f) {          // the attached ControlNet's forward first: its residuals feed this plan
+        cfgpp_unet* cn = u->ctrl;
+        CFGPP_REQUIRE(cn->img_rows > 0, "forward: a ControlNet is attached but has no control image (cfgpp_unet_image_condition)");
+        CFGPP_REQUIRE(cn->ctx_set && cn->ctx_rows == rows, "forward: the attached ControlNet's context is set for %d rows, the forward runs %d",
+                      cn->ctx_set ? cn->ctx_rows : 0, rows);
+        int e = cfgpp_unet_forward(cn, z, z_is_half, z_rows, t, eps_out, rows, stream);
+        if (e) return e;
+    }
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->in_t_dev = nullptr; u->out_eps = eps_out;
     if (u->tuned_rows != rows && igemm_autotune_enabled()) {      // first forward at this batch: in-situ tile tuning
         int e = u->tune_plan((hipStream_t)stream, rows); if (e) return e;
@@ -571,6 +792,8 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
     CFGPP_REQUIRE(u && u->finalized && u->ctx_set, "sample_graph: context not ready");
     CFGPP_REQUIRE(z && z0t && eps && eps_uc && eps_c && host_steps && n_steps > 0 && z_rows > 0, "sample_graph: bad args");
     CFGPP_REQUIRE(rows == u->ctx_rows && rows <= u->cfg.max_rows, "sample_graph: rows=%d but context was set for %d rows", rows, u->ctx_rows);
+    CFGPP_REQUIRE(!u->ctrl && !u->control, "sample_graph: a ControlNet is attached (a controlled step is not captured): detach it "
+                                            "(cfgpp_unet_attach_control(u, NULL, 0)) or run the eager loop");
     hipStream_t s = (hipStream_t)stream;
     CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
                   "sample_graph: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",

@@ -144,6 +144,28 @@ def lincomb(out, x, y, z, a: float, b: float, mode: int):
 # ----------------------------------------------------------------------------
 # UNet engine
 # ----------------------------------------------------------------------------
+def unet_config_c(cfg: UNetConfig, H: int, W: int, max_rows: int, out_channels: Optional[int] = None) -> UNetConfigC:
+    """the C struct of include/cfgpp.h for ``cfg`` at latent H x W; ``out_channels=0`` makes a ControlNet"""
+    cc = UNetConfigC()
+    cc.in_channels = cfg.in_channels
+    cc.out_channels = cfg.out_channels if out_channels is None else int(out_channels)
+    cc.num_levels = cfg.num_levels
+    for i in range(cfg.num_levels):
+        cc.block_out_channels[i] = cfg.block_out_channels[i]
+        cc.level_has_attn[i] = cfg.level_has_attn[i]
+        cc.transformer_depth[i] = cfg.transformer_depth[i]
+        cc.num_heads[i] = cfg.num_heads[i]
+    cc.layers_per_block = cfg.layers_per_block
+    cc.cross_attention_dim = cfg.cross_attention_dim
+    cc.addition_embed = cfg.addition_embed
+    cc.addition_time_embed_dim = cfg.addition_time_embed_dim
+    cc.addition_pooled_dim = cfg.addition_pooled_dim
+    cc.norm_groups = cfg.norm_groups
+    cc.sample_h, cc.sample_w = int(H), int(W)
+    cc.max_rows = int(max_rows)
+    return cc
+
+
 class HipUNet:
     """Hand-written HIP UNet behind the C ABI.  One instance per device."""
 
@@ -158,22 +180,7 @@ class HipUNet:
         self.max_rows = int(max_rows)
         H, W = sample_hw if sample_hw is not None else (cfg.sample_size, cfg.sample_size)
         self.H, self.W = int(H), int(W)
-        cc = UNetConfigC()
-        cc.in_channels, cc.out_channels = cfg.in_channels, cfg.out_channels
-        cc.num_levels = cfg.num_levels
-        for i in range(cfg.num_levels):
-            cc.block_out_channels[i] = cfg.block_out_channels[i]
-            cc.level_has_attn[i] = cfg.level_has_attn[i]
-            cc.transformer_depth[i] = cfg.transformer_depth[i]
-            cc.num_heads[i] = cfg.num_heads[i]
-        cc.layers_per_block = cfg.layers_per_block
-        cc.cross_attention_dim = cfg.cross_attention_dim
-        cc.addition_embed = cfg.addition_embed
-        cc.addition_time_embed_dim = cfg.addition_time_embed_dim
-        cc.addition_pooled_dim = cfg.addition_pooled_dim
-        cc.norm_groups = cfg.norm_groups
-        cc.sample_h, cc.sample_w = self.H, self.W
-        cc.max_rows = self.max_rows
+        cc = unet_config_c(cfg, self.H, self.W, self.max_rows)
         self._h = self.lib.cfgpp_unet_create(C.byref(cc), self.device)
         if not self._h:
             raise CfgppError("cfgpp_unet_create failed: " + _lib.last_error())
@@ -268,6 +275,12 @@ class HipUNet:
         check(self.lib.cfgpp_unet_forward(self._h, z.data_ptr(), 1 if z.dtype == torch.float16 else 0, zr, float(t),
                                           eps_out.data_ptr(), rows, _stream_ptr(z)), "cfgpp_unet_forward")
         return eps_out
+
+    def attach_control(self, cn, scale: float):
+        """attach ControlNet ``cn`` (a finalized :class:`cfgpp_amd.controlnet.HipControlNet`; None detaches) with
+        ``conditioning_scale`` (include/cfgpp.h: cfgpp_unet_attach_control).  Synchronises the device."""
+        check(self.lib.cfgpp_unet_attach_control(self._h, None if cn is None else cn._h, float(scale)), "cfgpp_unet_attach_control")
+        self._keep["control"] = cn          # the engine holds cn's raw handle
 
     def sample_graph_ddim(self, z: torch.Tensor, z0t: torch.Tensor, eps: torch.Tensor, eps_uc: torch.Tensor, eps_c: torch.Tensor,
                           steps, lam: float, tweedie_uc: bool, renoise_uc: bool):

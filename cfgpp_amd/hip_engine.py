@@ -57,6 +57,8 @@ class HipEngine:
                               build_id(_lib.LIB_PATH), lambda rows: self.unet.export_tuning(rows), lambda h, rows: self.unet.import_tuning(h, rows),
                               knobs=lambda: (int(self.unet.lib.cfgpp_igemm_tuner_state()),))
         self._ctx_key = None
+        self._ctx = None
+        self._control = None         # (HipControlNet, scale) while a control is set
         self._eps = None
         self._g_buf = None
         # opt-in guard for the first runs with a real checkpoint (real SDXL activations approach the fp16 maximum in the deep
@@ -82,6 +84,9 @@ class HipEngine:
             c = c.expand(B, -1, -1)
         ehs = torch.cat([uc, c], dim=0)
         self.unet.set_context(ehs, text_embeds, time_ids)
+        self._ctx = (ehs, text_embeds, time_ids)
+        if self._control is not None:         # the ControlNet sees the UNet's conditioning
+            self._control[0].set_context(ehs, text_embeds, time_ids)
         self._pins.load(2 * B)
         self.B = B
         if self._eps is None or int(self._eps.shape[0]) != 2 * B:      # kept across calls: a captured graph holds its address
@@ -91,6 +96,33 @@ class HipEngine:
         """inpaint UNets: the step-invariant [mask, masked-image latent] channels, [1 or B, in - out, H, W]
         (include/cfgpp.h: cfgpp_unet_image_condition).  Once per job, before predict / ddim_loop_graph."""
         self.unet.image_condition(cond)
+
+    # -- ControlNet ------------------------------------------------------------------
+    def set_control(self, cn, image: torch.Tensor, scale: float = 1.0):
+        """attach ControlNet ``cn`` (``controlnet.HipControlNet`` of this engine's geometry) with its control image
+        [1 or B, 3, 8H, 8W] in [0, 1] and ``controlnet_conditioning_scale``: every later ``predict`` runs the ControlNet first and
+        adds its residuals (include/cfgpp.h: cfgpp_unet_attach_control).  While a control is set the loops stay eager."""
+        cn.set_image(image)
+        if self._ctx is not None:
+            cn.set_context(*self._ctx)
+        self.unet.attach_control(cn, float(scale))
+        self._control = (cn, float(scale))
+
+    def clear_control(self):
+        """detach the ControlNet: predictions are the plain UNet's again, bit for bit"""
+        if self._control is not None:
+            self.unet.attach_control(None, 0.0)
+        self._control = None
+
+    def build_controlnet(self, spec, seed: int = 0):
+        """a ControlNet for this engine's geometry (max_batch, latent size, device): ``spec`` = "synthetic", a diffusers
+        ``controlnet/`` folder / safetensors file, or a state dict (controlnet.build_controlnet)"""
+        from .controlnet import build_controlnet
+        return build_controlnet(spec, self.cfg, 2 * self.max_batch, (self.H, self.W), self.device.index, seed)
+
+    @property
+    def control(self):
+        return self._control
 
     def predict(self, z: torch.Tensor, t: float):
         """(eps_uc, eps_c), each [B,4,H,W] fp16 - replaces predict_noise's UNet call + chunk(2)."""
@@ -104,7 +136,7 @@ class HipEngine:
     @property
     def graph_enabled(self) -> bool:
         """$CFGPP_GRAPH=1: DDIM loops without a callback run as hipGraph replays of one captured step (default off: see DESIGN.md)"""
-        return os.environ.get("CFGPP_GRAPH", "0") not in ("", "0")
+        return os.environ.get("CFGPP_GRAPH", "0") not in ("", "0") and self._control is None     # a controlled step is not captured
 
     def ddim_loop_graph(self, zt: torch.Tensor, steps, lam: float, tweedie_uc: bool, renoise_uc: bool, single: str = ""):
         """run the whole loop on (a persistent copy of) ``zt``; returns (z0t, zt) as fresh tensors.  ``single``: "uc" / "c" when the

@@ -22,7 +22,7 @@ import torch
 import torch.nn.functional as F
 
 from . import coeffs as K
-from .latent_diffusion import StableDiffusion, _progress
+from .latent_diffusion import StableDiffusion, _progress, controlled
 from .latent_sdxl import SDXL
 from .registry import Registry
 
@@ -77,6 +77,7 @@ class _InpaintMixin:
     """shared by the SD1.5 and SDXL classes: mask / source preparation, the start latent, the masked eager loop"""
 
     cfgpp = False
+    controllable = False        # ControlNet on inpaint UNets is not supported: sample() refuses control_image
 
     @property
     def inpaint_unet(self) -> bool:
@@ -157,6 +158,7 @@ class InpaintDDIM(_InpaintMixin, StableDiffusion):
     """SD1.5 inpainting, DDIM with CFG (eps_hat renoises)."""
 
     @torch.no_grad()
+    @controlled
     def sample(self, cfg_guidance=7.5, prompt=["", ""], src_img=None, mask=None, strength: float = 1.0, callback_fn=None,
                **kwargs):
         """``src_img`` [B or 1,3,8h,8w] in [-1, 1]; ``mask`` [B or 1,1,8h,8w] in [0, 1], 1 = repaint (binarized at 0.5).
@@ -194,6 +196,7 @@ class InpaintDDIMXL(_InpaintMixin, SDXL):
     ``prompt=[null, text]`` is taken for both towers.  ``return_latents=True`` returns the last z0t."""
 
     @torch.no_grad()
+    @controlled
     def sample(self, *args, **kwargs):
         p = kwargs.pop("prompt", None)
         if p is not None:

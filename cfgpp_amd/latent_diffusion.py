@@ -12,6 +12,8 @@ B independent chains; chain b equals the reference run with ``set_seed(s_b)``.
 """
 from __future__ import annotations
 
+import contextlib
+import functools
 import os
 import sys
 from typing import Any, Callable, Dict, List, Optional
@@ -38,6 +40,23 @@ class _SchedulerView:
         self.timesteps = tables.timesteps
         self.alphas_cumprod = tables.alphas_cumprod
         self.final_alpha_cumprod = tables.final_alpha_cumprod
+
+
+def controlled(sample):
+    """``sample(..., control_image=None, controlnet_conditioning_scale=1.0)``: with a control image, the solver's ControlNet
+    (``get_solver(..., controlnet=...)``) is attached to the engine for this call - every UNet prediction of the loop, whatever
+    the solver, follows it (diffusers StableDiffusion(XL)ControlNetPipeline, one net, non-guess mode); without one the engine
+    runs the plain UNet.  Solvers whose ``controllable`` is False (inversion, edit, inpaint) refuse a control image."""
+    @functools.wraps(sample)
+    def run(self, *args, **kwargs):
+        image = kwargs.pop("control_image", None)
+        scale = kwargs.pop("controlnet_conditioning_scale", 1.0)
+        if image is not None and not self.controllable:
+            raise ValueError(f"{type(self).__name__}.sample() does not take control_image: ControlNet conditioning is for the "
+                             "text-to-image solvers (inversion, edit and inpaint solvers refuse it)")
+        with self._control(image, scale):
+            return sample(self, *args, **kwargs)
+    return run
 
 
 def _progress(it, desc):
@@ -87,6 +106,14 @@ class StableDiffusion:
         self.engine = engine
         self.unet = engine
         self.work_device = getattr(engine, "device", torch.device("cpu"))
+        # ControlNet ("synthetic", a diffusers controlnet/ folder or safetensors file, or a state dict), built by the engine at
+        # its own max_batch and latent size; attached per sample() call that passes control_image
+        self.controlnet = None
+        cn = kwargs.get("controlnet")
+        if cn is not None:
+            if not hasattr(engine, "build_controlnet"):
+                raise ValueError(f"controlnet=...: the engine {type(engine).__name__} cannot build a ControlNet")
+            self.controlnet = engine.build_controlnet(cn, seed=kwargs.get("controlnet_seed", 0))
 
         # boundary components (off the per-step path)
         self.text_encoder = kwargs.get("text_encoder") or SyntheticTextEncoder(cfg.cross_attention_dim, None)
@@ -108,6 +135,26 @@ class StableDiffusion:
 
     def alpha(self, t):
         return self.tables.alpha(t)
+
+    controllable = True         # text-to-image: sample() takes control_image (see `controlled`)
+
+    @contextlib.contextmanager
+    def _control(self, image, scale):
+        eng = self.engine
+        if image is None:
+            if getattr(eng, "control", None) is not None:
+                eng.clear_control()
+            yield
+            return
+        if self.controlnet is None:
+            raise ValueError("control_image given, but the solver has no ControlNet: get_solver(..., controlnet=\"synthetic\" | path | state_dict)")
+        if not torch.is_tensor(image) or image.dim() != 4 or int(image.shape[1]) != 3:
+            raise ValueError(f"control_image must be a [1 or B, 3, 8h, 8w] tensor in [0, 1], got {getattr(image, 'shape', type(image))}")
+        eng.set_control(self.controlnet, image, float(scale))
+        try:
+            yield
+        finally:
+            eng.clear_control()
 
     @torch.no_grad()
     def get_text_embed(self, null_prompt, prompt):
@@ -409,6 +456,7 @@ class BaseDDIM(StableDiffusion):
     cfgpp = False
 
     @torch.no_grad()
+    @controlled
     def sample(self, cfg_guidance=7.5, prompt=["", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         B = int(c.shape[0])
@@ -427,6 +475,7 @@ class EulerCFGSolver(StableDiffusion):
     variant, solver = 0, "euler"
 
     @torch.no_grad()
+    @controlled
     def sample(self, cfg_guidance, prompt=["", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         den, x = self._kdiff_loop(uc, c, cfg_guidance, self.variant, self.solver, callback_fn, kwargs.get("seeds"))
@@ -442,6 +491,7 @@ class EulerAncestralCFGSolver(StableDiffusion):
     cfgpp, two_stage = False, False
 
     @torch.no_grad()
+    @controlled
     def sample(self, cfg_guidance, prompt=["", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         den, x = self._ancestral_loop(uc, c, cfg_guidance, self.cfgpp, self.two_stage, callback_fn, kwargs.get("seeds"))
@@ -465,6 +515,7 @@ class DPMpp2mCFGSolver(EulerCFGSolver):
 @register_solver("ddim_inversion")
 class InversionDDIM(BaseDDIM):
     """Invert with CFG then reconstruct (reference: latent_diffusion.py:506-558)."""
+    controllable = False
 
     def _invert(self, src_img, uc, c, cfg_guidance, kwargs):
         z0 = kwargs.get("src_latent")
@@ -473,6 +524,7 @@ class InversionDDIM(BaseDDIM):
         return self.inversion(z0, uc, c, cfg_guidance=cfg_guidance)
 
     @torch.no_grad()
+    @controlled
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         zt = self._invert(src_img, uc, c, cfg_guidance, kwargs)
@@ -488,6 +540,7 @@ class EditWordSwapDDIM(InversionDDIM):
     (reference: latent_diffusion.py:561-612)."""
 
     @torch.no_grad()
+    @controlled
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, src_c, tgt_c = self._embeds(prompt, kwargs, n_cond=2)
         zt = self._invert(src_img, uc, src_c, cfg_guidance, kwargs)

@@ -17,7 +17,7 @@ import torch
 from .registry import Registry
 from . import coeffs as K
 from .conditioning import SyntheticTextEncoder, as_list
-from .latent_diffusion import StableDiffusion, _progress
+from .latent_diffusion import StableDiffusion, _progress, controlled
 from .schedule import get_sigmas_karras
 from .unet_config import SDXL as SDXL_CFG
 
@@ -140,6 +140,7 @@ class SDXL(StableDiffusion):
         return {"text_embeds": te.to(self.work_device), "time_ids": ids.to(self.work_device)}
 
     @torch.no_grad()
+    @controlled
     def sample(self, prompt1=["", ""], prompt2=["", ""], cfg_guidance: float = 5.0,
                original_size: Optional[Tuple[int, int]] = None, crops_coords_top_left: Tuple[int, int] = (0, 0),
                target_size: Optional[Tuple[int, int]] = None, negative_original_size: Optional[Tuple[int, int]] = None,
@@ -349,8 +350,10 @@ class EulerLight(_LightningMixin, Euler, SDXLLightning):
 @register_solver("ddim_edit")
 class EditWardSwapDDIM(BaseDDIM):
     """Invert with the source prompt, regenerate with the target (reference: latent_sdxl.py:569-706)."""
+    controllable = False
 
     @torch.no_grad()
+    @controlled
     def sample(self, prompt1=["", "", ""], prompt2=["", "", ""], cfg_guidance: float = 5.0,
                original_size: Optional[Tuple[int, int]] = None, crops_coords_top_left: Tuple[int, int] = (0, 0),
                target_size: Optional[Tuple[int, int]] = None, negative_original_size: Optional[Tuple[int, int]] = None,

@@ -2,7 +2,7 @@
 
     python examples/text_to_img.py --prompt "a corgi" --method ddim_cfg++ --cfg_guidance 0.6 --NFE 50 \
         [--model sd15|sdxl|sdxl_lightning] [--unet_weights unet.safetensors --vae_weights vae.safetensors] \
-        [--batch 8] [--draw]
+        [--batch 8] [--draw] [--controlnet_dir <diffusers controlnet/ folder> --control_image edges.png]
 
 Differences from the reference, all additive: ``--unet_weights / --vae_weights`` (diffusers-layout safetensors;
 default = seeded synthetic weights, because no checkpoint exists offline), ``--batch`` (B chains with seeds
@@ -31,7 +31,17 @@ REFERENCE_FLAGS = (
     ("null_prompt", str, "low quality,jpeg artifacts,blurry,poorly drawn,ugly,worst quality,"), ("prompt", str, ""),
     ("cfg_guidance", float, 7.5), ("method", str, "ddim"), ("NFE", int, 50), ("seed", int, 42),
 )
-EXTRA_FLAGS = (("unet_weights", str, "synthetic"), ("vae_weights", str, None), ("model_dir", str, None), ("batch", int, 1))
+EXTRA_FLAGS = (("unet_weights", str, "synthetic"), ("vae_weights", str, None), ("model_dir", str, None), ("batch", int, 1),
+               ("controlnet_dir", str, None), ("control_image", str, None), ("controlnet_conditioning_scale", float, 1.0))
+
+
+def load_control_image(path, size):
+    """a PNG / JPEG -> [1, 3, h, w] in [0, 1]: converted to RGB and resized to the target size, no normalisation (diffusers'
+    ControlNet image processor: do_convert_rgb=True, do_normalize=False)"""
+    from PIL import Image
+    import numpy as np
+    img = Image.open(path).convert("RGB").resize((size[1], size[0]), Image.BICUBIC)
+    return torch.from_numpy(np.asarray(img, dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous()
 
 
 def main(argv=None, solver_kwargs=None) -> None:
@@ -60,6 +70,8 @@ def main(argv=None, solver_kwargs=None) -> None:
             if k.endswith("_weights") and getattr(args, k, None) not in (None, "synthetic"):
                 continue                                   # an explicit --unet_weights / --vae_weights wins
             kw[k] = v
+    if args.controlnet_dir:   # a local diffusers controlnet/ folder (config.json + safetensors); "synthetic" = seeded weights
+        kw["controlnet"] = args.controlnet_dir
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference
@@ -68,16 +80,28 @@ def main(argv=None, solver_kwargs=None) -> None:
         from cfgpp_amd.latent_sdxl import get_solver
         solver = get_solver(args.method, **kw)
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
-                               cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds)
+                               cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
+                               **_control_kwargs(args, solver))
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
         solver = get_solver(args.method, **kw)
-        result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds)
+        result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
+                               **_control_kwargs(args, solver))
 
     for i in range(result.shape[0]):
         name = "generated.png" if result.shape[0] == 1 else f"generated_{i}.png"
         save_image(result[i:i + 1], args.workdir / "result" / name, normalize=True)
     print(f"saved {result.shape[0]} image(s) to {args.workdir / 'result'}")
+
+
+def _control_kwargs(args, solver):
+    if not args.control_image:
+        return {}
+    if not args.controlnet_dir:
+        raise SystemExit("--control_image needs --controlnet_dir (a diffusers controlnet/ folder, or 'synthetic')")
+    h, w = solver.latent_hw
+    return dict(control_image=load_control_image(args.control_image, (8 * h, 8 * w)),
+                controlnet_conditioning_scale=args.controlnet_conditioning_scale)
 
 
 if __name__ == "__main__":

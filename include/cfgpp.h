@@ -187,6 +187,30 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
  * un-profiled run chose, so PMC passes see the same kernels without timing passes of their own. */
 int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set);
 
+/* ---- ControlNet (diffusers ControlNetModel with StableDiffusionControlNetPipeline / StableDiffusionXLControlNetPipeline:
+ * one net, non-guess mode).  No reference counterpart: the reference README points its users to other front ends for it. */
+
+/* A ControlNet is a cfgpp_unet made by cfgpp_unet_create with out_channels = 0 (it has no conv_out: its outputs are residuals)
+ * and in_channels = the latent channels - diffusers `ControlNetModel.from_pretrained(...)`.  It holds conv_in, the time
+ * (+ add_embedding) embedding, the down blocks and the mid block from the same diffusers keys as the UNet, no up path, plus
+ * `controlnet_cond_embedding.{conv_in,blocks.0-5,conv_out}` (ControlNetConditioningEmbedding with diffusers' default
+ * conditioning_embedding_out_channels (16, 32, 96, 256)) and the 1x1 zero convolutions `controlnet_down_blocks.N` (one per
+ * skip connection) and `controlnet_mid_block`.  load_tensor / missing / finalize / set_context / destroy work on it
+ * unchanged; cfgpp_unet_image_condition sets its control image (the pipeline's prepared `image`, step-invariant):
+ * fp16 [image_rows][3][8H][8W] in [0, 1], no normalisation (do_normalize=False), embedded once per job
+ * (`controlnet_cond = self.controlnet_cond_embedding(controlnet_cond)`) into an engine-owned buffer whose address never changes.
+ * Row r of the UNet batch uses image row (r % z_rows) % image_rows: the uncond and cond halves see the same image, as the
+ * pipeline's torch.cat([image] * 2) does.  Detach a ControlNet from every UNet before destroying it. */
+
+/* Attach ControlNet cn to UNet u (cn = NULL detaches).  While one is attached with scale != 0, cfgpp_unet_forward first runs
+ * cn's forward on the same stream with the same z, t and rows (ControlNetModel.forward: `down_block_res_samples` and
+ * `mid_block_res_sample`, each `* conditioning_scale`), then the UNet, whose skip connections and mid-block output receive
+ * them (UNet2DConditionModel.forward: `down_block_additional_residuals` / `mid_block_additional_residual`) in one launch after
+ * the mid block.  scale == 0 or no ControlNet: nothing extra is launched.  cn must match u's levels, channels, latent size
+ * and max_rows; cn's context (set_context) must be set for the same rows, and a forward before its control image is set is an
+ * error.  cfgpp_sample_graph_ddim refuses an engine with a ControlNet attached.  Synchronises the device. */
+int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale);
+
 /* Algorithmic FLOPs (2*MAC over conv/linear/attention matmuls) of one forward at `rows`. */
 double cfgpp_unet_flops(cfgpp_unet* u, int rows);
 /* Bytes of device memory held (weights + activations). */
