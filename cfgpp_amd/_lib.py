@@ -91,6 +91,9 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_igemm_gstat_written": (_I, []),
     "cfgpp_groupnorm_set_prestats": (None, [_I]),
     "cfgpp_groupnorm_prestats_enabled": (_I, []),
+    "cfgpp_unet_set_share_prefix": (None, [_I]),
+    "cfgpp_unet_share_prefix_enabled": (_I, []),
+    "cfgpp_unet_shared_prefix_ops": (_I, [_P, _I, _I]),
     "cfgpp_op_layernorm": (_I, [_P, _P, _P, _P, _L, _I, _F, _P]),
     "cfgpp_op_attention_prepare_vt": (_I, [_P, _I, _I, _I, _P]),
     "cfgpp_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

@@ -32,6 +32,15 @@ int cfgpp_op_igemm_gstat_written(void);
 /* 1 (default): the engines' GroupNorms take the producers' statistics whenever the producer wrote them; 0: always their own pass (A/B) */
 void cfgpp_groupnorm_set_prestats(int on);
 int cfgpp_groupnorm_prestats_enabled(void);
+/* Shared CFG prefix of the UNet forward (csrc/unet.hip).  1 (default): a call with rows == 2 * z_rows on a net without
+ * add_embedding whose first level has attention runs the plan ops between conv_in and the first cross-attention - whose inputs
+ * are the same for rows r and r + z_rows - on z_rows rows, then one fan-out launch copies the three live tensors onto the upper
+ * rows; 0: every op at `rows` (A/B).  Process-global, read by every forward / profile / graph capture. */
+void cfgpp_unet_set_share_prefix(int on);
+int cfgpp_unet_share_prefix_enabled(void);
+/* number of plan ops a forward at (rows, z_rows) runs at rows / 2 as things stand (0: the call does not share - switch off,
+ * rows != 2 * z_rows, or the net does not qualify: SDXL) */
+int cfgpp_unet_shared_prefix_ops(cfgpp_unet* u, int rows, int z_rows);
 /* development / A-B switch of the GroupNorm form: 0 auto, 1 always the two-launch form, 2 the one-launch
  * slab-in-registers kernel whenever the slab fits (csrc/norm_kernels.hip). */
 void cfgpp_groupnorm_set_mode(int mode);

@@ -47,6 +47,10 @@ struct CnAddEntry {
 };
 int cn_residual_add_launch(const CnAddEntry* tab, int n, long max_n8, int rows, float scale, hipStream_t s);
 
+// fan-out of the shared CFG prefix (small_kernels.hip; used by unet.hip): batch rows [0, h) of up to three fp16 buffers, each
+// contiguous in the batch row (row_elems[k] % 8 == 0), are copied onto rows [h, 2h) in one launch
+int fanout_rows_launch(half_t* const* p, const long* row_elems, int nseg, int h, hipStream_t s);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- activation layouts -----------------------------------------------------

@@ -9,6 +9,7 @@
 #include <functional>
 #include <map>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/cfgpp.h"
@@ -55,6 +56,16 @@ struct EngineBase {
     std::vector<int> plan_kind;     // 0 igemm (conv/linear), 1 attention, 2 norm (GN/LN), 3 small
     std::vector<double> plan_macs;
     std::vector<std::string> plan_desc;
+    // Shared CFG prefix (unet.hip): 1 = the op's inputs are the same for batch rows r and r + rows / 2 of a CFG call, so a call
+    // that shares runs it on the leading rows / 2 rows only; 2 = the fan-out copy that ends the prefix (runs only in such a call)
+    std::vector<char> plan_share;
+    // batch rows op i of `plan` runs at in a call at `rows`: THE one place that decides it - every walk over `plan` asks here.
+    // 0 = the op is not part of this call.
+    int rows_for(size_t i, int rows, bool shared) const {
+        const int m = i < plan_share.size() ? plan_share[i] : 0;
+        if (m == 0) return rows;
+        return shared ? rows / 2 : (m == 1 ? rows : 0);
+    }
     void tag(int kind, double macs, const std::string& desc = "") {
         plan_kind.resize(plan.size(), 3); plan_macs.resize(plan.size(), 0.0); plan_desc.resize(plan.size());
         if (!plan.empty()) { plan_kind.back() = kind; plan_macs.back() = macs; plan_desc.back() = desc; }
@@ -63,7 +74,9 @@ struct EngineBase {
     std::deque<int> cfg_hints;
     std::vector<int*> plan_hint;    // per plan op: its hint slot or null
     int tuned_rows = 0;
-    std::map<int, std::vector<int>> tuned_by_rows;      // batch rows -> pinned config per hint slot (re-used when the batch alternates)
+    bool tuned_shared = false;      // the pins in cfg_hints were taken with the shared prefix at rows / 2
+    // (batch rows, shared prefix) -> pinned config per hint slot (re-used when the batch or the mode alternates)
+    std::map<std::pair<int, bool>, std::vector<int>> tuned_by_rows;
     int* new_hint(bool in_main_plan) {
         cfg_hints.push_back(0);
         int* h = &cfg_hints.back();
@@ -73,12 +86,13 @@ struct EngineBase {
     // Times every hinted launch of `plan` in place - HIP events between the launches of a real forward on
     // `s`, two passes per candidate tile config - and pins the fastest (>= 3 % better than the heuristic).
     // The forward is idempotent, so the passes leave the same activations behind as one plain forward.
-    int tune_plan(hipStream_t s, int rows) {
-        auto cached = tuned_by_rows.find(rows);
+    int tune_plan(hipStream_t s, int rows, bool shared = false) {
+        const auto key = std::make_pair(rows, shared);
+        auto cached = tuned_by_rows.find(key);
         if (cached != tuned_by_rows.end() && cached->second.size() == cfg_hints.size()) {
             size_t k = 0;
             for (int& h : cfg_hints) h = cached->second[k++];
-            tuned_rows = rows;
+            tuned_rows = rows; tuned_shared = shared;
             return 0;
         }
         static const int cands[] = {0, 1, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 20, 24, 25, 26, 27, 28};
@@ -98,7 +112,7 @@ struct EngineBase {
             for (int rep = 0; rep < 2 && rc == 0; ++rep) {
                 if (hipEventRecord(ev[0], s) != hipSuccess) rc = -1;
                 for (size_t i = 0; i < n && rc == 0; ++i) {
-                    rc = plan[i](s, rows);
+                    rc = plan[i](s, rows_for(i, rows, shared));
                     if (plan_hint[i]) applied[i] = (char)igemm_last_hint_applied();
                     if (rc == 0 && hipEventRecord(ev[i + 1], s) != hipSuccess) rc = -1;
                 }
@@ -133,8 +147,8 @@ struct EngineBase {
         for (int& h : cfg_hints) h = 0;
         for (size_t i = 0; i < n; ++i) if (plan_hint[i]) *plan_hint[i] = bestc[i];
         for (auto& e : ev) hipEventDestroy(e);
-        if (rc == 0) tuned_by_rows[rows] = std::vector<int>(cfg_hints.begin(), cfg_hints.end());
-        tuned_rows = rows;
+        if (rc == 0) tuned_by_rows[key] = std::vector<int>(cfg_hints.begin(), cfg_hints.end());
+        tuned_rows = rows; tuned_shared = shared;
         return rc;
     }
     // activation pool, keyed by shape (halo stays zero for ever); every buffer travels with its statistics buffer

@@ -3,6 +3,8 @@
 // added-condition MLPs and the batched time_emb_proj (M = UNet batch rows <= 64).
 // None of them matters for FLOPs; they exist so that the whole forward stays on
 // the device, asynchronous, with no host round trip.
+#include <algorithm>
+
 #include "common.h"
 
 namespace {
@@ -299,7 +301,49 @@ __global__ void f16_to_f32_rows_kernel(const half_t* __restrict__ in, float* __r
     }
 }
 
+// ---------------------------------------------------------------------------
+// Fan-out that ends the shared CFG prefix (unet.hip): up to three buffers whose batch rows [0, h) were computed once for both
+// halves of a classifier-free-guidance batch; rows [h, 2h) become a copy of them.  Every buffer is contiguous in the batch
+// row, so a segment is one flat copy of n16 16-byte units onto the n16 units behind it (blockIdx.y = segment).  Four
+// independent 16-byte loads per thread and pass, plain vector stores.
+// ---------------------------------------------------------------------------
+struct FanoutArgs {
+    uint4* p[3];
+    long n16[3];
+};
+
+__global__ void __launch_bounds__(256)
+fanout_rows_kernel(FanoutArgs a) {
+    const long n = a.n16[blockIdx.y];
+    const uint4* __restrict__ src = a.p[blockIdx.y];
+    uint4* __restrict__ dst = a.p[blockIdx.y] + n;
+    const long T = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    for (; i + 3 * T < n; i += 4 * T) {
+        const uint4 v0 = src[i], v1 = src[i + T], v2 = src[i + 2 * T], v3 = src[i + 3 * T];
+        dst[i] = v0; dst[i + T] = v1; dst[i + 2 * T] = v2; dst[i + 3 * T] = v3;
+    }
+    for (; i < n; i += T) dst[i] = src[i];
+}
+
 }  // namespace
+
+// rows [0, h) of each p[k] ([>= 2h][row_elems[k]] fp16, row_elems % 8 == 0, 16-byte aligned) are copied onto rows [h, 2h); nseg <= 3
+int fanout_rows_launch(half_t* const* p, const long* row_elems, int nseg, int h, hipStream_t s) {
+    CFGPP_REQUIRE(p && row_elems && nseg > 0 && nseg <= 3 && h > 0, "fanout_rows: bad args");
+    FanoutArgs a{};
+    long most = 0;
+    for (int k = 0; k < nseg; ++k) {
+        CFGPP_REQUIRE(p[k] && row_elems[k] > 0 && row_elems[k] % 8 == 0 && ((uintptr_t)p[k] & 15) == 0, "fanout_rows: segment %d is not made of 16-byte units", k);
+        a.p[k] = reinterpret_cast<uint4*>(p[k]);
+        a.n16[k] = (long)h * (row_elems[k] / 8);
+        most = std::max(most, a.n16[k]);
+    }
+    dim3 grid((unsigned)std::min<long>(cdiv(most, 256 * 4), 2048), (unsigned)nseg);
+    hipLaunchKernelGGL(fanout_rows_kernel, grid, dim3(256), 0, s, a);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 
 // ---------------------------------------------------------------------------

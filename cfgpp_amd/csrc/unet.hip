@@ -30,6 +30,21 @@ struct cfgpp_unet : EngineBase {
     struct Graph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<Graph> graphs;              // most recently used last; at most 4 (an invert + edit job alternates between two)
     int tuned_serial = 0;                   // bumps whenever the pins of the current batch change (a graph bakes the tiles it captured)
+    // ---- shared CFG prefix.  A CFG call runs rows = 2 * z_rows with row r reading latent r % z_rows; without add_embedding the
+    // time embedding is one vector for every row, so rows r and r + z_rows first differ at the first cross-attention (the text
+    // context).  The plan ops from down_blocks.0.resnets.0 to the attn2.to_q projection of down_blocks.0.attentions.0 (plan_share
+    // == 1) then run on the leading z_rows rows only and one fan-out launch (plan_share == 2) copies the three live tensors - the
+    // token stream, the head-major Q and the resnet output the transformer's proj_out adds - onto the upper rows.
+    int prefix_ops = 0;                     // plan ops marked 1 (0: this net has no shareable prefix - SDXL)
+    double prefix_macs_per_row = 0;         // their MACs per batch row (matmuls and attention)
+    int ran_shared = -1;                    // mode of the most recent forward / profile (-1: none yet)
+    bool shares(int rows, int z_rows) const;
+    // run-time mode of a call: bumps tuned_serial when it differs from the last one, so no captured graph replays the other plan
+    bool enter_call(int rows, int z_rows) {
+        const bool sh = shares(rows, z_rows);
+        if (ran_shared != (int)sh) { if (ran_shared >= 0) ++tuned_serial; ran_shared = (int)sh; }
+        return sh;
+    }
     static void destroy(Graph& g) { if (g.exec) hipGraphExecDestroy(g.exec); if (g.graph) hipGraphDestroy(g.graph); g.exec = nullptr; g.graph = nullptr; }
     void drop_graphs() { for (auto& g : graphs) destroy(g); graphs.clear(); }
     ~cfgpp_unet() { drop_graphs(); if (cap_stream) hipStreamDestroy(cap_stream); }
@@ -63,6 +78,9 @@ struct cfgpp_unet : EngineBase {
     cfgpp_unet* ctrl = nullptr; float ctrl_scale = 0.f;
     CnAddEntry* d_ctrl_tab = nullptr; long ctrl_max_n8 = 0;
 };
+
+static int g_share_prefix = 1;
+bool cfgpp_unet::shares(int rows, int z_rows) const { return g_share_prefix && prefix_ops > 0 && rows == 2 * z_rows; }
 
 namespace {
 
@@ -463,6 +481,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         return out;
     };
     int cross_block_counter = 0;
+    long prefix_from = -1;          // >= 0: plan index where the shared CFG prefix starts; the next transformer ends it
     auto transformer = [&](const std::string& p, const Tensor& x, int depth, int nheads, int lvl) {
         half_t* const HQ = u->hq[lvl]; half_t* const HK = u->hk[lvl]; half_t* const HVT = u->hvt[lvl];
         const int C = x.C, tok = x.H * x.W, d = C / nheads, dp = round_up(d, 32);
@@ -510,6 +529,25 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
             // cross-attention
             P.layernorm(u->tok_x, u->tok_ln, l2g, l2b, tok, C);
             P.heads(u->tok_ln, C, wq2, C, tok, 0, C, nheads, HQ, nullptr, nullptr, q_pad, k_pad);
+            if (prefix_from >= 0) {
+                // end of the shared CFG prefix: the cross-attention below is the first op that sees the text context.  Live from
+                // here on: tok_x (residual stream), HQ (its queries) and x (the residual of proj_out), each contiguous in the row.
+                u->plan_share.assign(u->plan.size(), 0);
+                for (size_t i = (size_t)prefix_from; i < u->plan.size(); ++i) {
+                    u->plan_share[i] = 1; ++u->prefix_ops;
+                    if (i < u->plan_macs.size()) u->prefix_macs_per_row += u->plan_macs[i];
+                }
+                half_t* const fp0 = u->tok_x; half_t* const fp1 = HQ; half_t* const fp2 = x.p;
+                const long fe0 = (long)tok * C, fe1 = (long)nheads * q_pad * dp, fe2 = (long)(x.H + 2) * (x.W + 2) * C;
+                u->plan.push_back([=](hipStream_t s, int h) {
+                    if (h <= 0) return 0;                  // a call that does not share
+                    half_t* const fp[3] = {fp0, fp1, fp2}; const long fe[3] = {fe0, fe1, fe2};
+                    return fanout_rows_launch(fp, fe, 3, h, s);
+                });
+                u->plan_share.push_back(2);
+                u->tag(3, 0.0, "cfg fan-out tok_x + HQ + resid HW=" + std::to_string(tok) + " C=" + std::to_string(C));
+                prefix_from = -1;
+            }
             {
                 cfgpp_unet* uu = u;
                 u->attn_macs_per_row += 2.0 * (double)nheads * tok * 77 * d;
@@ -569,6 +607,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         const int co = c.block_out_channels[i];
         const std::string p = "down_blocks." + std::to_string(i);
         for (int j = 0; j < c.layers_per_block; ++j) {
+            if (i == 0 && j == 0 && !per_row_temb && c.level_has_attn[0]) prefix_from = (long)u->plan.size();
             Tensor y = resblock(p + ".resnets." + std::to_string(j), x, nullptr, co);
             if (c.level_has_attn[i]) {
                 Tensor z = transformer(p + ".attentions." + std::to_string(j), y, c.transformer_depth[i], c.num_heads[i], i);
@@ -601,6 +640,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         CFGPP_REQUIRE(B.ok, "finalize: %s", B.err.c_str());
         CFGPP_HIP_CHECK(hipDeviceSynchronize());
         u->plan_kind.resize(u->plan.size(), 3); u->plan_macs.resize(u->plan.size(), 0.0); u->plan_desc.resize(u->plan.size());
+        u->plan_share.resize(u->plan.size(), 0);
         u->finalized = true;
         return 0;
     }
@@ -664,6 +704,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
     CFGPP_REQUIRE(skips.empty(), "finalize: internal error, %d skips left", (int)skips.size());
     CFGPP_HIP_CHECK(hipDeviceSynchronize());
     u->plan_kind.resize(u->plan.size(), 3); u->plan_macs.resize(u->plan.size(), 0.0); u->plan_desc.resize(u->plan.size());
+    u->plan_share.resize(u->plan.size(), 0);
     u->finalized = true;
     return 0;
 }
@@ -769,11 +810,12 @@ int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
         if (e) return e;
     }
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->in_t_dev = nullptr; u->out_eps = eps_out;
-    if (u->tuned_rows != rows && igemm_autotune_enabled()) {      // first forward at this batch: in-situ tile tuning
-        int e = u->tune_plan((hipStream_t)stream, rows); if (e) return e;
+    const bool shared = u->enter_call(rows, z_rows);
+    if ((u->tuned_rows != rows || u->tuned_shared != shared) && igemm_autotune_enabled()) {      // first forward at this batch and mode: in-situ tile tuning
+        int e = u->tune_plan((hipStream_t)stream, rows, shared); if (e) return e;
         ++u->tuned_serial;
     }
-    for (auto& op : u->plan) { int e = op((hipStream_t)stream, rows); if (e) return e; }
+    for (size_t i = 0; i < u->plan.size(); ++i) { int e = u->plan[i]((hipStream_t)stream, u->rows_for(i, rows, shared)); if (e) return e; }
     return 0;
 }
 
@@ -812,6 +854,7 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
         CFGPP_REQUIRE(u->d_step_tab, "sample_graph: out of device memory");
         u->step_tab_cap = cap;
     }
+    u->enter_call(rows, z_rows);           // a graph captured in the other mode (switch flipped since) must not hit: the serial moves
     const cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
     auto same = [&](const cfgpp_unet::GraphKey& k) {
         return k.z == want.z && k.z0t == want.z0t && k.eps == want.eps && k.euc == want.euc && k.ec == want.ec && k.z_half == want.z_half &&
@@ -835,7 +878,8 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
         int rc = 0;
         if (he == hipSuccess) {
             rc = step_advance_launch(u->d_step_tab, u->d_step_idx, u->d_step_cur, u->cap_stream);
-            for (size_t i = 0; i < u->plan.size() && rc == 0; ++i) rc = u->plan[i](u->cap_stream, rows);
+            const bool shared = u->shares(rows, z_rows);      // the mode of the eager forward above
+            for (size_t i = 0; i < u->plan.size() && rc == 0; ++i) rc = u->plan[i](u->cap_stream, u->rows_for(i, rows, shared));
             if (rc == 0) rc = step_ddim_dev_launch(z, z0t, eps_uc, eps_c, 1, z_is_half, lam, u->d_step_cur + 1, tweedie_uc, renoise_uc, n, u->cap_stream);
             he = hipStreamEndCapture(u->cap_stream, &g.graph);
         }
@@ -873,26 +917,34 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->out_eps = eps_out;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = u->plan.size();
+    // the rows every op really runs at: times, FLOPs and descriptions below are those of the work that was done.  (The tiles are
+    // whatever the last forward pinned: profile after a forward of the same mode.)
+    const bool shared = u->enter_call(rows, z_rows);
+    std::vector<int> op_rows(n);
+    for (size_t i = 0; i < n; ++i) op_rows[i] = u->rows_for(i, rows, shared);
     std::vector<hipEvent_t> ev(n + 1);
     for (auto& e : ev) CFGPP_HIP_CHECK(hipEventCreate(&e));
     CFGPP_HIP_CHECK(hipEventRecord(ev[0], s));
     int rc = 0;
-    for (size_t i = 0; i < n && rc == 0; ++i) { rc = u->plan[i](s, rows); if (rc == 0 && hipEventRecord(ev[i + 1], s) != hipSuccess) rc = -1; }
+    for (size_t i = 0; i < n && rc == 0; ++i) { rc = u->plan[i](s, op_rows[i]); if (rc == 0 && hipEventRecord(ev[i + 1], s) != hipSuccess) rc = -1; }
     if (rc == 0 && hipStreamSynchronize(s) != hipSuccess) rc = -1;
     for (int k = 0; k < 4; ++k) { out_ms[k] = 0; out_flops[k] = 0; out_launches[k] = 0; }
     if (rc == 0) {
         for (size_t i = 0; i < n; ++i) {
+            if (op_rows[i] == 0) continue;               // not part of this call (the fan-out of a call that does not share)
             float ms = 0.f; hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
             const int k = u->plan_kind[i];
-            out_ms[k] += ms; out_flops[k] += 2.0 * u->plan_macs[i] * rows; out_launches[k] += 1;
+            out_ms[k] += ms; out_flops[k] += 2.0 * u->plan_macs[i] * op_rows[i]; out_launches[k] += 1;
         }
         if (detail && detail_cap > 0) {      // one line per launch: index, family, description, us, GFLOP
             std::string txt;
             for (size_t i = 0; i < n; ++i) {
+                if (op_rows[i] == 0) continue;
                 float ms = 0.f; hipEventElapsedTime(&ms, ev[i], ev[i + 1]);
                 char line[256];
-                snprintf(line, sizeof(line), "%zu\t%d\t%s\t%.1f\t%.3f\n", i, u->plan_kind[i], u->plan_desc[i].c_str(), ms * 1e3,
-                         2.0 * u->plan_macs[i] * rows * 1e-9);
+                const std::string desc = u->plan_desc[i] + (op_rows[i] != rows ? " rows=" + std::to_string(op_rows[i]) : std::string());
+                snprintf(line, sizeof(line), "%zu\t%d\t%s\t%.1f\t%.3f\n", i, u->plan_kind[i], desc.c_str(), ms * 1e3,
+                         2.0 * u->plan_macs[i] * op_rows[i] * 1e-9);
                 txt += line;
             }
             const long ncopy = std::min<long>((long)txt.size(), detail_cap - 1);
@@ -911,12 +963,14 @@ int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set) {
     const int n = (int)u->cfg_hints.size();
     CFGPP_REQUIRE(cap >= n, "unet_tuning: buffer of %d for %d launches", cap, n);
     if (set) {
-        u->tuned_by_rows[rows] = std::vector<int>(hints, hints + n);
+        // an import may arrive before any forward, when the mode of the calls to come is not known: both modes of this batch get
+        // the list (pins only decide speed, and a launch rejects a tile it cannot run)
+        for (int sh = 0; sh < 2; ++sh) u->tuned_by_rows[std::make_pair(rows, sh != 0)] = std::vector<int>(hints, hints + n);
         if (u->tuned_rows == rows) u->tuned_rows = 0;      // re-install on the next forward
         ++u->tuned_serial;
         return n;
     }
-    auto it = u->tuned_by_rows.find(rows);
+    auto it = u->tuned_by_rows.find(std::make_pair(rows, u->ran_shared == 1));       // the mode the engine last ran in
     if (it == u->tuned_by_rows.end()) { cfgpp_set_error("unet_tuning: batch %d has not been tuned", rows); return -3; }
     std::copy(it->second.begin(), it->second.end(), hints);
     return n;
@@ -924,7 +978,16 @@ int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set) {
 
 double cfgpp_unet_flops(cfgpp_unet* u, int rows) {
     if (!u || !u->finalized) return 0.0;
-    return 2.0 * (u->macs_per_row + u->attn_macs_per_row) * rows;
+    // the prefix a CFG call shares is computed once for both halves: counted once when the most recent forward shared it
+    const double once = u->ran_shared == 1 ? u->prefix_macs_per_row * (rows / 2) : 0.0;
+    return 2.0 * ((u->macs_per_row + u->attn_macs_per_row) * rows - once);
+}
+
+void cfgpp_unet_set_share_prefix(int on) { g_share_prefix = on ? 1 : 0; }
+int cfgpp_unet_share_prefix_enabled(void) { return g_share_prefix; }
+int cfgpp_unet_shared_prefix_ops(cfgpp_unet* u, int rows, int z_rows) {
+    if (!u || !u->finalized) return 0;
+    return u->shares(rows, z_rows) ? u->prefix_ops : 0;
 }
 double cfgpp_unet_device_bytes(cfgpp_unet* u) { return u ? u->dev_bytes : 0.0; }
 

@@ -334,7 +334,21 @@ class HipUNet:
             raise CfgppError("cfgpp_unet_tuning: " + _lib.last_error())
 
     def flops(self, rows: int) -> float:
+        """algorithmic FLOPs of one forward at ``rows``; the shared CFG prefix counts once when the most recent forward shared it"""
         return float(self.lib.cfgpp_unet_flops(self._h, int(rows)))
+
+    def shared_prefix_ops(self, rows: int, z_rows: int) -> int:
+        """plan ops a forward at (rows, z_rows) runs at rows / 2 (0: it does not share; cfgpp_debug.h)"""
+        return int(self.lib.cfgpp_unet_shared_prefix_ops(self._h, int(rows), int(z_rows)))
 
     def device_bytes(self) -> float:
         return float(self.lib.cfgpp_unet_device_bytes(self._h))
+
+
+def set_share_prefix(on: bool):
+    """process-global A/B switch of the shared CFG prefix (default on; cfgpp_debug.h: cfgpp_unet_set_share_prefix)"""
+    _lib.load().cfgpp_unet_set_share_prefix(1 if on else 0)
+
+
+def share_prefix_enabled() -> bool:
+    return bool(_lib.load().cfgpp_unet_share_prefix_enabled())

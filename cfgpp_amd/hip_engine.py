@@ -55,7 +55,8 @@ class HipEngine:
         # tile pins persist across processes (tune_cache.py): only the first process on a box runs the in-situ tuning passes
         self._pins = PinCache(getattr(cfg, "name", type(cfg).__name__), (self.H, self.W), torch.cuda.get_device_properties(self.device).name,
                               build_id(_lib.LIB_PATH), lambda rows: self.unet.export_tuning(rows), lambda h, rows: self.unet.import_tuning(h, rows),
-                              knobs=lambda: (int(self.unet.lib.cfgpp_igemm_tuner_state()),))
+                              knobs=lambda: (int(self.unet.lib.cfgpp_igemm_tuner_state()),),
+                              mode=lambda rows: "shared" if self.unet.shared_prefix_ops(rows, rows // 2) else "")
         self._ctx_key = None
         self._ctx = None
         self._control = None         # (HipControlNet, scale) while a control is set

@@ -6,7 +6,9 @@ fastest tile per launch.  Every candidate gives bit-identical results, so the
 pins only decide speed - and they are a property of (model, latent size, batch
 rows, GPU model, kernel build), not of the process.  ``PinCache`` keeps them in
 ``$CFGPP_TUNE_CACHE`` (default ``~/.cache/cfgpp_amd``; ``0`` or empty = off) as
-``tune_<model>_<HxW>_r<rows>_<device>_<build>.json``: only the first process on a
+``tune_<model>_<HxW>_r<rows>_<device>_<build>[_<mode>].json`` (mode: ``shared`` when
+the forwards at that batch run the shared CFG prefix at half the rows - pins taken
+at M/2 are another plan's): only the first process on a
 box pays for the tuning passes, later ones import the pins before their first
 forward and the C ABI's "never synchronises" holds from the first call on.
 ``CFGPP_AUTOTUNE=0`` keeps its meaning (heuristic tiles, nothing pinned, nothing
@@ -55,7 +57,7 @@ class PinCache:
 
     def __init__(self, model: str, latent_hw, device_name: str, build: str,
                  export_fn: Callable[[int], List[int]], import_fn: Callable[[List[int], int], None], directory: Optional[str] = None,
-                 knobs: Optional[Callable[[], tuple]] = None):
+                 knobs: Optional[Callable[[], tuple]] = None, mode: Optional[Callable[[int], str]] = None):
         self.dir = cache_dir() if directory is None else directory
         self.tag = "_".join(re.sub(r"[^A-Za-z0-9.]+", "-", str(x)) for x in (model, f"{latent_hw[0]}x{latent_hw[1]}"))
         self.dev = re.sub(r"[^A-Za-z0-9.]+", "-", device_name)
@@ -65,9 +67,11 @@ class PinCache:
         self._tries = {}            # rows -> forwards after which the engine still had no pins to export
         self._knobs = knobs         # () -> tuple of the tuner's switches (candidate mask, big tiles, ...); pins are only persisted
         self._knobs_default = knobs() if knobs is not None else None      # while it still equals its value at construction
+        self._mode = mode           # rows -> "" or the name of the plan variant the forwards at `rows` run ("shared"): part of the key
 
     def path(self, rows: int) -> str:
-        return os.path.join(self.dir, f"tune_{self.tag}_r{rows}_{self.dev}_{self.build}.json")
+        mode = self._mode(rows) if self._mode is not None else ""
+        return os.path.join(self.dir, f"tune_{self.tag}_r{rows}_{self.dev}_{self.build}{'_' + mode if mode else ''}.json")
 
     def load(self, rows: int) -> bool:
         """before the first forward at `rows`: install the pins a previous process left (True when it did)"""

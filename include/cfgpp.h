@@ -184,7 +184,9 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
 
 /* Export (set = 0) / import (set = 1) the per-launch tile configs pinned by the in-situ tuning at batch `rows`
  * (one int per implicit-GEMM launch, plan order); returns the number of slots.  A profiled run imports what the
- * un-profiled run chose, so PMC passes see the same kernels without timing passes of their own. */
+ * un-profiled run chose, so PMC passes see the same kernels without timing passes of their own.  Pins are kept per
+ * (rows, shared CFG prefix or not): export returns those of the mode the engine last ran in, an import (which may come
+ * before any forward) installs the list for both modes of that batch. */
 int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set);
 
 /* ---- ControlNet (diffusers ControlNetModel with StableDiffusionControlNetPipeline / StableDiffusionXLControlNetPipeline:
@@ -211,7 +213,9 @@ int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set);
  * error.  cfgpp_sample_graph_ddim refuses an engine with a ControlNet attached.  Synchronises the device. */
 int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale);
 
-/* Algorithmic FLOPs (2*MAC over conv/linear/attention matmuls) of one forward at `rows`. */
+/* Algorithmic FLOPs (2*MAC over conv/linear/attention matmuls) of one forward at `rows`.  When the most recent forward shared
+ * the CFG prefix (rows == 2 * z_rows on a net without add_embedding: the ops before the first cross-attention ran once for
+ * both halves), those ops count once - the figure is the work that was done. */
 double cfgpp_unet_flops(cfgpp_unet* u, int rows);
 /* Bytes of device memory held (weights + activations). */
 double cfgpp_unet_device_bytes(cfgpp_unet* u);

@@ -23,6 +23,7 @@ _lib.load().cfgpp_attention_set_stagger(int(os.environ.get("ATTN_STAGGER", "0"))
 _lib.load().cfgpp_attention_set_cross(int(os.environ.get("ATTN_CROSS", "1")))
 _lib.load().cfgpp_attention_set_dma(int(os.environ.get("ATTN_MODE", "1")))
 _lib.load().cfgpp_igemm_set_tail_split(int(os.environ.get("TAIL_SPLIT", "1")))      # 2 = round-1 slice count (rounded up)
+_lib.load().cfgpp_unet_set_share_prefix(int(os.environ.get("SHARE_PREFIX", "1")))    # 0: the CFG prefix at full rows too (A/B)
 eng = HipEngine(name, max_batch=rows // 2, latent_hw=(hw, hw) if hw else None)
 cfg = eng.cfg
 B = rows // 2
@@ -41,7 +42,7 @@ for _ in range(N):
         i, kind, desc, us, gf = line.split("\t")
         a = agg.setdefault((kind, desc), [0, 0.0, 0.0]); a[0] += 1; a[1] += float(us); a[2] += float(gf)
 tot = sum(a[1] for a in agg.values()) / N
-print(f"# {name} rows={rows} staging={'glds' if staging else 'reg'} total {tot/1e3:.2f} ms/forward")
+print(f"# {name} rows={rows} staging={'glds' if staging else 'reg'} share_prefix={eng.unet.shared_prefix_ops(rows, B)} ops total {tot/1e3:.2f} ms/forward")
 for (kind, desc), (cnt, us, gf) in sorted(agg.items(), key=lambda kv: -kv[1][1]):
     print(f"{us/N/1e3:8.3f} ms  {100*us/N/tot:5.1f}%  x{cnt//N:<3d} {gf/us*1e3 if us else 0:7.1f} TF/s  [{kind}] {desc}")
 # wall clock of back-to-back forwards (launch gaps included) vs the sum of per-launch times above
