@@ -60,6 +60,7 @@ PROTOTYPES = {
     "cfgpp_unet_profile": (_I, [_P, _P, _I, _I, _F, _P, _I, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_char_p, _L]),
     "cfgpp_unet_tuning": (_I, [_P, _I, C.POINTER(C.c_int), _I, _I]),
     "cfgpp_unet_attach_control": (_I, [_P, _P, _F]),
+    "cfgpp_unet_lora": (_I, [_P, C.c_char_p, _P, _P, _I, _P]),
     "cfgpp_unet_flops": (C.c_double, [_P, _I]),
     "cfgpp_unet_device_bytes": (C.c_double, [_P]),
     "cfgpp_vae_create": (_P, [_I, _I, _I, _F, _I]),
@@ -69,7 +70,6 @@ PROTOTYPES = {
     "cfgpp_vae_decode": (_I, [_P, _P, _P, _I, _P]),
     "cfgpp_vae_decode_image": (_I, [_P, _P, _P, _I, _P]),
     "cfgpp_vae_encode": (_I, [_P, _P, _P, _P, _P, _I, _P]),
-    "cfgpp_vae_profile": (_I, [_P, _P, _P, _I, _P, C.c_char_p, C.c_long]),
     "cfgpp_vae_flops": (C.c_double, [_P, _I]),
     "cfgpp_text_create": (_P, [_I, _I, _I, _I, _I, _I, _I, _I, _I]),
     "cfgpp_text_destroy": (None, [_P]),
@@ -104,6 +104,8 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_residual_add": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int), _I, _I, _F, _P]),
     "cfgpp_op_residual_nchw": (_I, [_P, _P, _I, _I, _I, _I, _F, _P]),
     "cfgpp_controlnet_residual": (_I, [_P, _I, _F, _P, _I, C.POINTER(C.c_int), _P]),
+    "cfgpp_vae_profile": (_I, [_P, _P, _P, _I, _P, C.c_char_p, C.c_long]),
+    "cfgpp_unet_read_weight": (_I, [_P, C.c_char_p, _P]),
     "cfgpp_op_vae_posterior": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _F, _P]),
     "cfgpp_op_conv_out": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_out_ex": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _F, _F, _I, _P]),

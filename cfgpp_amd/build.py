@@ -25,6 +25,7 @@ SOURCES = [
     ("big4p_kernel.hip", []),
     ("attn_kernel.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),   # scores are consumed by VALU: keep MFMA results in VGPRs
     ("controlnet_kernels.hip", ["-ffp-contract=off"]),   # the residual add is torch's fp16 `s + r * scale` bit for bit
+    ("lora_kernels.hip", []),
     ("unet.hip", []),
     ("vae.hip", []),
     ("text.hip", []),

@@ -79,6 +79,15 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
         if cin == 9:
             from .unet_config import SD15_INPAINT, SDXL_INPAINT
             kw["unet_config"] = SDXL_INPAINT if sdxl else SD15_INPAINT
+    lora = _first(os.path.join(d, "pytorch_lora_weights.safetensors"), os.path.join(d, "lora.safetensors"))
+    if lora:
+        # a LoRA file next to the model (diffusers' save_lora_weights name, or lora.safetensors): merged into the UNet at scale 1
+        # (get_solver(lora=...)); its text-encoder entries, if any, are set aside - the text encoders take no adapter.  Said aloud,
+        # because it changes what the checkpoint computes; the CLIs' --lora replaces it, a caller drops kw["lora"] to opt out
+        logging.getLogger("cfgpp_amd").warning("%s: merging the LoRA file found next to the model (%s) at scale 1; pass --lora / "
+                                               "lora= to choose adapters yourself", d, os.path.basename(lora))
+        kw["lora"] = [(lora, 1.0)]
+        kw["lora_ignore_text_encoder"] = True
     if vae:
         kw["vae_weights"] = vae
     else:

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._lib import CfgppError, check
-from .engine import _stream_ptr, unet_config_c
+from .engine import HipUNet, _stream_ptr, unet_config_c
 from .unet_config import UNetConfig, param_shapes
 from .weights import synth_tensor
 
@@ -146,6 +146,16 @@ class HipControlNet:
         check(self.lib.cfgpp_unet_finalize(self._h), "cfgpp_unet_finalize (ControlNet)")
         self.finalized = True
         return self
+
+    # LoRA on the ControlNet's own matrices (same entry point and slot table as the UNet's: engine.HipUNet.lora / read_weight)
+    def _matrix_shape(self, key: str):
+        shapes = getattr(self, "_shapes", None)
+        if shapes is None:
+            shapes = self._shapes = dict(controlnet_param_shapes(self.cfg))
+        return shapes.get(key)
+
+    lora = HipUNet.lora
+    read_weight = HipUNet.read_weight
 
     def set_context(self, ehs: torch.Tensor, text_embeds: Optional[torch.Tensor] = None, time_ids: Optional[torch.Tensor] = None):
         """the UNet's conditioning (``HipUNet.set_context``): the ControlNet sees the same text (and SDXL added) conditioning"""

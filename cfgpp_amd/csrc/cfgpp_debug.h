@@ -95,6 +95,16 @@ int cfgpp_op_residual_nchw(const void* src, float* out, int rows, int H, int W, 
  * dense fp32 NCHW buffer out [rows][C][H][W].  Returns the number of residuals when out is NULL. */
 int cfgpp_controlnet_residual(cfgpp_unet* cn, int i, float scale, float* out, int rows, int* hwc_out, void* stream);
 
+/* the CURRENT weight of matrix parameter `key` (base, or base + the adapters merged by cfgpp_unet_lora), read back from the
+ * repacked device layout and un-repacked to checkpoint order: host_fp16_out holds [O][I][kh][kw] / [O][I] fp16.  Same keys and
+ * refusals as cfgpp_unet_lora.  Synchronises the device. */
+int cfgpp_unet_read_weight(cfgpp_unet* u, const char* key, void* host_fp16_out);
+
+/* per-launch timing of the VAE decoder (a diagnostic: scripts and HipVAE.profile; the UNet's twin cfgpp_unet_profile feeds the
+ * benchmark and stays in include/cfgpp.h): one decode (image post-processing included) with a HIP event between every launch of the decoder plan; `detail` receives one
+ * line per launch: index \t family (0 igemm, 1 attention GEMMs, 2 norm / softmax, 3 small) \t description \t us \t GFLOP */
+int cfgpp_vae_profile(cfgpp_vae* v, const void* z, void* img, int B, void* stream, char* detail, long detail_cap);
+
 /* quant_conv (1x1, 8->8) + DiagonalGaussian posterior on the encoder's 8-channel conv_out (fp32 NCHW). */
 int cfgpp_op_vae_posterior(const float* conv_out, const float* qw, const float* qb, const float* noise, float* z,
                            float* moments, int B, int HW, float scale, void* stream);

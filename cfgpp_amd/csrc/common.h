@@ -51,6 +51,11 @@ int cn_residual_add_launch(const CnAddEntry* tab, int n, long max_n8, int rows, 
 // contiguous in the batch row (row_elems[k] % 8 == 0), are copied onto rows [h, 2h) in one launch
 int fanout_rows_launch(half_t* const* p, const long* row_elems, int nseg, int h, hipStream_t s);
 
+// LoRA merge (lora_kernels.hip; used by unet.hip): dst = fp16(float(base) + up [O][rank] x down [rank][I * taps]) over the O rows of
+// one parameter in its repacked layout.  kind 0: [O][I * taps] as in the checkpoint, 1: conv3x3 columns [I/64][tap][64], 2: GEGLU rows
+int lora_merge_launch(const half_t* base, half_t* dst, const float* up, const float* down, int rank, int kind, long O, long I,
+                      int taps, hipStream_t s);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- activation layouts -----------------------------------------------------

@@ -41,11 +41,25 @@ struct Tensor {   // halo-padded NHWC fp16 activation
 
 using Op = std::function<int(hipStream_t, int /*rows*/)>;
 
+// Where one fp16 matrix parameter lives on the device after the repack (recorded by the Builder while it uploads): what an
+// in-place update of that parameter (cfgpp_unet_lora) or a read-back in checkpoint order (cfgpp_unet_read_weight) has to know.
+enum { SLOT_PLAIN = 0, SLOT_CONV3 = 1, SLOT_GEGLU = 2, SLOT_MEMBER = 3 };
+struct WeightSlot {
+    half_t* ptr = nullptr;      // the uploaded matrix (of a row-concatenated one: its first row, not this member's)
+    int kind = SLOT_PLAIN;      // plain [N][K] | conv3x3 [O][I/64][tap][64] | GEGLU row interleave | member of a row concatenation
+    long row_off = 0;           // SLOT_MEMBER: first row of this parameter inside the concatenated matrix
+    long O = 0, I = 0; int taps = 1;
+    half_t* base = nullptr;     // the rows as finalize uploaded them, saved on the first merge into this parameter
+    long K() const { return I * taps; }
+    half_t* rows() const { return ptr + row_off * K(); }
+};
+
 
 struct EngineBase {
     int max_rows = 1;
     int norm_groups = 32;
     std::map<std::string, HostParam> params;
+    std::map<std::string, WeightSlot> slots;     // every fp16 matrix parameter the Builder uploaded
     std::vector<void*> allocs;
     double dev_bytes = 0;
     double macs_per_row = 0;        // conv/linear MACs per batch row per forward
@@ -248,6 +262,13 @@ struct Builder {
         if (hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) { ok = false; err = "hipMemcpy failed"; }
         return d;
     }
+    // the slot of `key` ([O][I * taps] in checkpoint order) at row `row_off` of the uploaded matrix d
+    void slot(const std::string& key, half_t* d, int kind, long row_off = 0) {
+        const HostParam& p = u->params[key];
+        WeightSlot w; w.ptr = d; w.kind = kind; w.row_off = row_off; w.O = p.shape[0];
+        w.taps = kind == SLOT_CONV3 ? 9 : 1; w.I = p.numel() / (w.O * w.taps);
+        u->slots[key] = w;
+    }
     void drop(const std::string& key) { auto& p = u->params[key]; std::vector<half_t>().swap(p.h); std::vector<float>().swap(p.f); }
 
     float* f32(const std::string& key) {
@@ -257,7 +278,7 @@ struct Builder {
     // [N][K] as is (linear, or conv1x1 OIHW)
     half_t* linear(const std::string& key) {
         HostParam* p = get(key); if (!p) return nullptr;
-        half_t* d = upload(p->h); drop(key); return d;
+        half_t* d = upload(p->h); drop(key); slot(key, d, SLOT_PLAIN); return d;
     }
     // OIHW -> [O][I/64][kh*kw][64]  (K order of the implicit GEMM: channel-block major, tap minor)
     half_t* conv3(const std::string& key) {
@@ -267,7 +288,7 @@ struct Builder {
         for (long o = 0; o < O; ++o)
             for (long i = 0; i < I; ++i)
                 for (int t = 0; t < 9; ++t) r[(size_t)o * 9 * I + ((i >> 6) * 9 + t) * 64 + (i & 63)] = p->h[((size_t)o * I + i) * 9 + t];
-        half_t* d = upload(r); drop(key); return d;
+        half_t* d = upload(r); drop(key); slot(key, d, SLOT_CONV3); return d;
     }
     // concat rows of several [n_i][K] matrices
     std::vector<half_t> concat_host(const std::vector<std::string>& keys) {
@@ -278,7 +299,11 @@ struct Builder {
     }
     half_t* concat(const std::vector<std::string>& keys) {
         std::vector<half_t> r = concat_host(keys);
-        return ok ? upload(r) : nullptr;
+        if (!ok) return nullptr;
+        half_t* d = upload(r);
+        long row = 0;
+        for (auto& k : keys) { slot(k, d, SLOT_MEMBER, row); row += u->params[k].shape[0]; }
+        return d;
     }
     // GEGLU packing: within every 64 packed rows, [0,32) value rows f, [32,64) gate rows 4C+f
     bool geglu_host(const std::string& pfx, long C, std::vector<half_t>& rw, std::vector<float>& rb) {
@@ -299,6 +324,7 @@ struct Builder {
         std::vector<half_t> rw; std::vector<float> rb;
         if (!geglu_host(pfx, C, rw, rb)) return;
         *w = upload(rw); *b = upload(rb);
+        slot(pfx + ".weight", *w, SLOT_GEGLU);
     }
 };
 

@@ -396,6 +396,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         }
         u->temb_total = off;
         w_temb_all = B.upload(wa); b_temb_all = B.upload(ba);
+        for (auto& rn : res_names) B.slot(rn + ".time_emb_proj.weight", w_temb_all, SLOT_MEMBER, temb_off[rn]);
         u->d_temb_all = (float*)u->dmalloc((size_t)R * off * sizeof(float));
     }
     const bool per_row_temb = c.addition_embed != 0;
@@ -990,6 +991,72 @@ int cfgpp_unet_shared_prefix_ops(cfgpp_unet* u, int rows, int z_rows) {
     return u->shares(rows, z_rows) ? u->prefix_ops : 0;
 }
 double cfgpp_unet_device_bytes(cfgpp_unet* u) { return u ? u->dev_bytes : 0.0; }
+
+// ---- LoRA: in-place merge into the repacked weights -------------------------------
+// the slot of `key`, or null with the reason (naming the key) in the error string
+static WeightSlot* lora_slot(cfgpp_unet* u, const char* key, const char* who) {
+    if (!u || !key) { cfgpp_set_error("%s: null argument", who); return nullptr; }
+    if (!u->finalized) { cfgpp_set_error("%s: %s: the engine is not finalized (weights are merged into the uploaded, repacked matrices)", who, key); return nullptr; }
+    const std::string k = key;
+    if (k == "conv_in.weight" || k == "conv_out.weight") {
+        cfgpp_set_error("%s: %s runs on the fp32 small-kernel path and takes no adapter", who, key); return nullptr;
+    }
+    auto it = u->params.find(k);
+    if (it == u->params.end()) { cfgpp_set_error("%s: unknown key %s", who, key); return nullptr; }
+    if (!it->second.is_matrix) { cfgpp_set_error("%s: %s is a 1-D parameter (bias / norm): adapters apply to matrices", who, key); return nullptr; }
+    auto sl = u->slots.find(k);
+    if (sl == u->slots.end()) { cfgpp_set_error("%s: %s is not held as an fp16 matrix (fp32 direct-convolution path)", who, key); return nullptr; }
+    return &sl->second;
+}
+
+int cfgpp_unet_lora(cfgpp_unet* u, const char* key, const float* up, const float* down, int rank, void* stream) {
+    WeightSlot* w = lora_slot(u, key, "lora");
+    if (!w) return -2;
+    CFGPP_REQUIRE(rank >= 0, "lora: %s: rank %d", key, rank);
+    CFGPP_REQUIRE(rank == 0 || (up && down), "lora: %s: rank %d with a null up / down matrix", key, rank);
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bytes = (size_t)w->O * w->K() * sizeof(half_t);
+    if (rank == 0) {                        // restore; a parameter never merged into still is its base
+        if (w->base) CFGPP_HIP_CHECK(hipMemcpyAsync(w->rows(), w->base, bytes, hipMemcpyDeviceToDevice, s));
+        return 0;
+    }
+    if (!w->base) {                         // first merge into this parameter: keep what finalize uploaded (until destroy)
+        half_t* b = (half_t*)u->dmalloc(bytes, false);
+        CFGPP_REQUIRE(b, "lora: %s: out of device memory for the saved base (%zu bytes)", key, bytes);
+        CFGPP_HIP_CHECK(hipMemcpyAsync(b, w->rows(), bytes, hipMemcpyDeviceToDevice, s));
+        w->base = b;
+    }
+    const int kind = w->kind == SLOT_MEMBER ? SLOT_PLAIN : w->kind;
+    int e = lora_merge_launch(w->base, w->rows(), up, down, rank, kind, w->O, w->I, w->taps, s);
+    if (e) { const std::string m = cfgpp_last_error(); cfgpp_set_error("lora: %s: %s", key, m.c_str()); }
+    return e;
+}
+
+// test / debugging hook (cfgpp_debug.h): the current weight of `key`, un-repacked to checkpoint order ([O][I][kh][kw] / [O][I])
+int cfgpp_unet_read_weight(cfgpp_unet* u, const char* key, void* host_fp16_out) {
+    WeightSlot* w = lora_slot(u, key, "read_weight");
+    if (!w) return -2;
+    CFGPP_REQUIRE(host_fp16_out, "read_weight: %s: null output", key);
+    const long O = w->O, Kc = w->K(), I = w->I; const int taps = w->taps;
+    std::vector<half_t> r((size_t)O * Kc);
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    CFGPP_HIP_CHECK(hipDeviceSynchronize());
+    CFGPP_HIP_CHECK(hipMemcpy(r.data(), w->rows(), r.size() * sizeof(half_t), hipMemcpyDeviceToHost));
+    half_t* out = (half_t*)host_fp16_out;
+    for (long p = 0; p < O; ++p) {
+        long o = p;
+        if (w->kind == SLOT_GEGLU) { const long q = p & 63; o = (p >> 6) * 32 + (q & 31) + (q >= 32 ? O / 2 : 0); }
+        const half_t* src = &r[(size_t)p * Kc];
+        half_t* dst = out + (size_t)o * Kc;
+        if (w->kind == SLOT_CONV3) {
+            for (long i = 0; i < I; ++i) for (int t = 0; t < taps; ++t) dst[i * taps + t] = src[((i >> 6) * taps + t) * 64 + (i & 63)];
+        } else {
+            std::memcpy(dst, src, Kc * sizeof(half_t));
+        }
+    }
+    return 0;
+}
 
 // ---- single-op wrappers for tests ----------------------------------------------
 // test hook: the next cfgpp_op_igemm launches write GroupNorm statistics of their output (IGemmArgs::gstat) into `buf`

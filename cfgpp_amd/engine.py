@@ -276,6 +276,47 @@ class HipUNet:
                                           eps_out.data_ptr(), rows, _stream_ptr(z)), "cfgpp_unet_forward")
         return eps_out
 
+    # -- LoRA ----------------------------------------------------------------------
+    def _matrix_shape(self, key: str):
+        from .unet_config import param_shapes
+        shapes = getattr(self, "_shapes", None)
+        if shapes is None:
+            shapes = self._shapes = dict(param_shapes(self.cfg))
+        return shapes.get(key)
+
+    def lora(self, key: str, up: Optional[torch.Tensor], down: Optional[torch.Tensor]):
+        """weight ``key`` = fp16(base + up @ down) in place on the device (include/cfgpp.h: cfgpp_unet_lora).  ``up`` [O, rank],
+        ``down`` [rank, I*kh*kw] (OIHW flattening), any float dtype / device: they are made fp32 on the engine's device.
+        ``up is None`` (or rank 0) restores the base bit for bit.  After a change of attn2.to_k / to_v call ``set_context`` again."""
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if up is None or int(up.shape[1]) == 0:
+            check(self.lib.cfgpp_unet_lora(self._h, key.encode(), None, None, 0, stream), f"cfgpp_unet_lora({key})")
+            return
+        shape = self._matrix_shape(key)
+        if shape is not None and len(shape) in (2, 4):         # (anything else: the engine's own refusal names the key)
+            O, K = int(shape[0]), 1
+            for d in shape[1:]:
+                K *= int(d)
+            if up.dim() != 2 or down.dim() != 2 or int(up.shape[0]) != O or int(down.shape[1]) != K or int(up.shape[1]) != int(down.shape[0]):
+                raise CfgppError(f"lora({key}): up {tuple(up.shape)} / down {tuple(down.shape)} do not fit the weight {tuple(shape)} "
+                                 f"(up [{O}, rank], down [rank, {K}])")
+        up = up.to(device=dev, dtype=torch.float32).contiguous()
+        down = down.to(device=dev, dtype=torch.float32).contiguous()
+        check(self.lib.cfgpp_unet_lora(self._h, key.encode(), up.data_ptr(), down.data_ptr(), int(up.shape[1]), stream),
+              f"cfgpp_unet_lora({key})")
+        # up / down are released here: the merge is enqueued on the stream torch's caching allocator orders their memory by, so a
+        # later allocation cannot reuse it before the kernel ran, and no adapter copy stays resident on the device
+
+    def read_weight(self, key: str) -> torch.Tensor:
+        """the current weight of ``key`` in checkpoint order, fp16 on the host (cfgpp_debug.h: cfgpp_unet_read_weight)"""
+        shape = self._matrix_shape(key)
+        if shape is None:
+            raise CfgppError(f"read_weight: unknown key {key}")
+        out = torch.empty(tuple(shape), dtype=torch.float16)
+        check(self.lib.cfgpp_unet_read_weight(self._h, key.encode(), out.data_ptr()), f"cfgpp_unet_read_weight({key})")
+        return out
+
     def attach_control(self, cn, scale: float):
         """attach ControlNet ``cn`` (a finalized :class:`cfgpp_amd.controlnet.HipControlNet`; None detaches) with
         ``conditioning_scale`` (include/cfgpp.h: cfgpp_unet_attach_control).  Synchronises the device."""

@@ -59,6 +59,8 @@ class HipEngine:
                               mode=lambda rows: "shared" if self.unet.shared_prefix_ops(rows, rows // 2) else "")
         self._ctx_key = None
         self._ctx = None
+        from .lora import LoraState
+        self._lora = LoraState(cfg, self.unet.lora)
         self._control = None         # (HipControlNet, scale) while a control is set
         self._eps = None
         self._g_buf = None
@@ -124,6 +126,23 @@ class HipEngine:
     @property
     def control(self):
         return self._control
+
+    # -- LoRA ------------------------------------------------------------------------
+    def set_lora(self, adapters, ignore_text_encoder: bool = False):
+        """``adapters``: list of ``(parsed | safetensors path | state dict, scale)``; ``[]`` restores the base weights.  One merge
+        kernel per touched weight (lora.LoraState); an attached ControlNet is left alone.  The weights' addresses do not move, so
+        tile pins and captured graphs stay valid; the conditioning has to be set again (``lora_epoch`` is part of the solvers'
+        context-cache key): the cross-attention K / V^T are computed from attn2.to_k / to_v."""
+        self._lora.set(adapters, ignore_text_encoder=ignore_text_encoder)
+        return self
+
+    @property
+    def lora_epoch(self) -> int:
+        return self._lora.epoch
+
+    @property
+    def lora_adapters(self):
+        return list(self._lora.adapters)
 
     def predict(self, z: torch.Tensor, t: float):
         """(eps_uc, eps_c), each [B,4,H,W] fp16 - replaces predict_noise's UNet call + chunk(2)."""

@@ -51,6 +51,9 @@ def controlled(sample):
     def run(self, *args, **kwargs):
         image = kwargs.pop("control_image", None)
         scale = kwargs.pop("controlnet_conditioning_scale", 1.0)
+        lora_scale = kwargs.pop("lora_scale", None)
+        if lora_scale is not None:          # shorthand: every adapter of the solver at this scale, from this job on
+            self.set_lora_scale(lora_scale)
         if image is not None and not self.controllable:
             raise ValueError(f"{type(self).__name__}.sample() does not take control_image: ControlNet conditioning is for the "
                              "text-to-image solvers (inversion, edit and inpaint solvers refuse it)")
@@ -115,6 +118,9 @@ class StableDiffusion:
                 raise ValueError(f"controlnet=...: the engine {type(engine).__name__} cannot build a ControlNet")
             self.controlnet = engine.build_controlnet(cn, seed=kwargs.get("controlnet_seed", 0))
 
+        if kwargs.get("lora"):              # [(safetensors path | state dict | parsed, scale), ...] merged into the UNet on the device
+            self.set_lora(kwargs["lora"], ignore_text_encoder=kwargs.get("lora_ignore_text_encoder", False))
+
         # boundary components (off the per-step path)
         self.text_encoder = kwargs.get("text_encoder") or SyntheticTextEncoder(cfg.cross_attention_dim, None)
         self.vae = kwargs.get("vae")
@@ -137,6 +143,27 @@ class StableDiffusion:
         return self.tables.alpha(t)
 
     controllable = True         # text-to-image: sample() takes control_image (see `controlled`)
+
+    # ------------------------------------------------------------------ LoRA
+    def set_lora(self, adapters, ignore_text_encoder: bool = False):
+        """merge ``adapters`` = ``[(safetensors path | state dict | lora.parse_lora result, scale), ...]`` into the engine's UNet
+        (``[]``: back to the base weights).  Takes effect with the next prediction; the conditioning cache follows the engine's
+        ``lora_epoch``."""
+        if not hasattr(self.engine, "set_lora"):
+            raise ValueError(f"lora=...: the engine {type(self.engine).__name__} cannot merge LoRA adapters")
+        self.engine.set_lora(adapters or [], ignore_text_encoder=ignore_text_encoder)
+
+    def set_lora_scale(self, scale: float):
+        """every adapter of the current set at ``scale`` (``sample(..., lora_scale=)``)"""
+        eng = self.engine
+        if not hasattr(eng, "set_lora"):
+            raise ValueError(f"lora_scale=...: the engine {type(eng).__name__} cannot merge LoRA adapters")
+        cur = eng.lora_adapters
+        if any(float(s) != float(scale) for _, s in cur):
+            eng.set_lora([(p, float(scale)) for p, _ in cur])
+
+    def _lora_epoch(self) -> int:
+        return int(getattr(self.engine, "lora_epoch", 0))
 
     @contextlib.contextmanager
     def _control(self, image, scale):
@@ -199,7 +226,7 @@ class StableDiffusion:
             raise ValueError("predict_noise needs at least one of uc / c")
         a = c if uc is None else uc
         b = uc if c is None else c
-        key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version)
+        key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch())
         if getattr(self, "_ctx_key", None) != key:
             self._set_context(a, b)
             self._ctx_key = key

@@ -106,7 +106,7 @@ class SDXL(StableDiffusion):
         b = uc if c is None else c
         te, ti = added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]
         key = (a.data_ptr(), b.data_ptr(), te.data_ptr(), ti.data_ptr(), tuple(te.shape), tuple(a.shape), tuple(b.shape),
-               a._version, b._version, te._version, ti._version)
+               a._version, b._version, te._version, ti._version, self._lora_epoch())
         if getattr(self, "_ctx_key", None) != key:
             B = max(int(a.shape[0]), int(b.shape[0]))
             rows = 2 * B

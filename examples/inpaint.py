@@ -42,6 +42,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     for flag, kind, default in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(f"--{flag}", type=kind, default=default)
     ap.add_argument("--model", default="sd15", choices=("sd15", "sdxl"))
+    ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
+                    help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--inpaint_unet", action="store_true", help="synthetic 9-channel inpaint UNet instead of the 4-channel one")
     args = ap.parse_args(argv)
     if args.mask_path is None:
@@ -71,6 +73,10 @@ def main(argv=None, solver_kwargs=None) -> None:
             if k.endswith("_weights") and getattr(args, k, None) not in (None, "synthetic"):
                 continue                                   # an explicit --unet_weights / --vae_weights wins
             kw[k] = v
+    if args.lora:
+        from cfgpp_amd.lora import parse_cli
+        kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
+        kw.pop("lora_ignore_text_encoder", None)
     kw.update(solver_kwargs or {})
     solver = get_inpaint_solver(args.method, model=args.model, **kw)
     common = dict(src_img=img, mask=mask, strength=args.strength, cfg_guidance=args.cfg_guidance, seeds=[args.seed], callback_fn=None)

@@ -50,6 +50,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     for flag, kind, default in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(f"--{flag}", type=kind, default=default)
     ap.add_argument("--model", default="sd15", choices=("sd15", "sd20", "sdxl", "sdxl_lightning"))
+    ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
+                    help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
     args = ap.parse_args(argv)
 
@@ -72,6 +74,10 @@ def main(argv=None, solver_kwargs=None) -> None:
             kw[k] = v
     if args.controlnet_dir:   # a local diffusers controlnet/ folder (config.json + safetensors); "synthetic" = seeded weights
         kw["controlnet"] = args.controlnet_dir
+    if args.lora:
+        from cfgpp_amd.lora import parse_cli
+        kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
+        kw.pop("lora_ignore_text_encoder", None)
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference

@@ -49,6 +49,8 @@ def main(argv=None, solver_kwargs=None) -> int:
     for flag, kind, default in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(f"--{flag}", type=kind, default=default)
     ap.add_argument("--model", default="sd15", choices=("sd15", "sd20", "sdxl", "sdxl_lightning"))
+    ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
+                    help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--no_draw", action="store_true", help="skip the per-step draw_noisy / draw_tweedie decodes")
     args = ap.parse_args(argv)
 
@@ -75,6 +77,10 @@ def main(argv=None, solver_kwargs=None) -> int:
             if k.endswith("_weights") and getattr(args, k, None) not in (None, "synthetic"):
                 continue                                   # an explicit --unet_weights / --vae_weights wins
             kw[k] = v
+    if args.lora:
+        from cfgpp_amd.lora import parse_cli
+        kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
+        kw.pop("lora_ignore_text_encoder", None)
     kw.update(solver_kwargs or {})
     xl = args.model in ("sdxl", "sdxl_lightning")
     if xl:

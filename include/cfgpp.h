@@ -213,6 +213,22 @@ int cfgpp_unet_tuning(cfgpp_unet* u, int rows, int* hints, int cap, int set);
  * error.  cfgpp_sample_graph_ddim refuses an engine with a ControlNet attached.  Synchronises the device. */
 int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale);
 
+/* LoRA: merge a low-rank update into one matrix of a FINALIZED engine, in place on the device, in the repacked layout the
+ * kernels read: W(key) = fp16(float(base) + up x down), the product accumulated in fp32 and rounded once, `base` being the
+ * weight finalize uploaded (saved device-to-device on the first merge into `key`, counted in cfgpp_unet_device_bytes, kept
+ * until destroy - so every call starts from the same base and repeated merges do not drift).  key: a diffusers weight name of
+ * the UNet (e.g. "down_blocks.1.attentions.0.transformer_blocks.0.attn2.to_k.weight"); up [O][rank], down [rank][I * kh * kw]
+ * (the checkpoint's own OIHW flattening), both fp32 on the device, with the adapters' scales (alpha / rank, user scale) folded
+ * in by the caller and several adapters concatenated along the rank axis.  rank == 0 restores the base bit for bit.  Weight
+ * addresses do not move: tile pins and captured graphs stay valid; after a change of attn2.to_k / to_v call
+ * cfgpp_unet_set_context again (the cross-attention K / V^T are computed there).  Works on a ControlNet-mode engine too.
+ * Refused (error naming the key, weight unchanged): conv_in.weight / conv_out.weight (fp32 small-kernel path), 1-D parameters,
+ * unknown keys, rank < 0, an engine that is not finalized.  The entry point receives pointers and a rank only: the CALLER
+ * guarantees that up holds O * rank and down rank * I * kh * kw floats for this key's weight (the Python binding checks the
+ * shapes against the UNet's parameter table and refuses a mismatch by key).  Asynchronous on `stream`; up / down must stay
+ * valid until the launch ran (stream-ordered allocations freed after the call are fine). */
+int cfgpp_unet_lora(cfgpp_unet* u, const char* key, const float* up, const float* down, int rank, void* stream);
+
 /* Algorithmic FLOPs (2*MAC over conv/linear/attention matmuls) of one forward at `rows`.  When the most recent forward shared
  * the CFG prefix (rows == 2 * z_rows on a net without add_embedding: the ops before the first cross-attention ran once for
  * both halves), those ops count once - the figure is the work that was done. */
@@ -237,9 +253,6 @@ int cfgpp_vae_decode_image(cfgpp_vae* v, const void* z, void* img, int B, void* 
  * img [B][3][8h][8w] f32, noise [B][4][h][w] f32 or NULL (posterior mean), z [B][4][h][w] f32,
  * moments [B][8][h][w] f32 or NULL (mean | logvar clamped to [-30, 20]). */
 int cfgpp_vae_encode(cfgpp_vae* v, const void* img, const void* noise, void* z, void* moments, int B, void* stream);
-/* one decode (image post-processing included) with a HIP event between every launch of the decoder plan; `detail` receives one
- * line per launch: index \t family (0 igemm, 1 attention GEMMs, 2 norm / softmax, 3 small) \t description \t us \t GFLOP */
-int cfgpp_vae_profile(cfgpp_vae* v, const void* z, void* img, int B, void* stream, char* detail, long detail_cap);
 double cfgpp_vae_flops(cfgpp_vae* v, int B);
 double cfgpp_vae_encode_flops(cfgpp_vae* v, int B);
 double cfgpp_vae_device_bytes(cfgpp_vae* v);
