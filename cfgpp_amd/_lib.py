@@ -140,6 +140,7 @@ DEBUG_PROTOTYPES = {
     "cfgpp_attention_set_dma": (None, [_I]),
     "cfgpp_attention_set_stagger": (None, [_I]),
     "cfgpp_attention_set_cross": (None, [_I]),
+    "cfgpp_attention_last_launch": (None, [C.POINTER(C.c_int)]),
 }
 
 _lib = None

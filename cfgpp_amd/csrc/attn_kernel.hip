@@ -32,7 +32,7 @@
 //     applied to the per-lane SOURCE chunk, on a 2-stage ring (32 KB: FOUR workgroups per CU since round 4; rounds 2-3: 3 stages, three), one
 //     raw s_barrier per tile, counted vmcnt.
 //   * other head dims (80, 160): attn_kernel, register-staged double buffering, padded LDS rows.
-// Cross-attention (77 keys padded to 128) uses the same kernel with nk_valid = 77.
+// At most 128 keys with dp = 64 (the 77 text tokens of cross-attention) take xattn64_kernel below: K / V^T resident, one pass.
 // softmax statistics and accumulation are fp32; P is rounded to fp16 for the PV
 // product (same as the reference's SDPA flash path under fp16 autocast).
 #include "common.h"
@@ -44,7 +44,8 @@ namespace {
 // (exact in fp16 / fp32: a floating-point scale; O and the denominator carry the same factor and it cancels in O / l).
 // On random data a NEW running max appears in ~2/3 of the tiles of a 32-query wave, but it beats the old one by < 2;
 // re-referencing only on a jump > 5 removes ~50 VALU instructions from 2/3 of the tiles.  The rare branch is covered
-// by tests/test_gpu_configs.py::test_attention_online_softmax_rescale_branch (a key that jumps by ~100).
+// by tests/test_gpu_configs.py::test_attention_online_softmax_rescale_branch (a key that jumps by ~100) and, for every
+// kernel that has the branch, by the planted late keys of tests/test_gpu_attention.py.
 constexpr float RESCALE_THR = 5.0f;
 
 struct AttnArgs {
@@ -169,7 +170,7 @@ attn_kernel(const AttnArgs a) {
                     s[qt][kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[qt][ks], ks == 0 ? negm[qt] : s[qt][kt], 0, 0, 0);
             }
         }
-        if (tail != 0 && t == ntiles - 1) {      // wave-uniform: mask keys >= nk_valid (cross-attention, 77 keys)
+        if (tail != 0 && t == ntiles - 1) {      // wave-uniform: mask keys >= nk_valid of a partial last tile (nk % 64 != 0)
             const int kbase = t * 64 + 4 * hi;
 #pragma unroll
             for (int qt = 0; qt < QT; ++qt)
@@ -393,7 +394,10 @@ attn64_kernel(const AttnArgs a) {
                 }
             }
         }
-        if (tail != 0 && t == ntiles - 1) {      // wave-uniform: mask keys >= nk_valid (cross-attention, 77 keys)
+        // wave-uniform: mask keys >= nk_valid of a partial last tile.  With the default switches this kernel sees nk > 128 only
+        // (<= 128 keys, the 77 text tokens included, go to xattn64_kernel), so the mask runs when nk % 64 != 0: 144 tokens of a
+        // 12 x 12 map, or any shape under cfgpp_attention_set_cross(0)
+        if (tail != 0 && t == ntiles - 1) {
             const int kbase = t * 64 + 4 * hi;
 #pragma unroll
             for (int kt = 0; kt < 2; ++kt)
@@ -694,12 +698,19 @@ static int g_attn_dma = 1;       // dp = 64: 1 = LDS-DMA kernel, 0 = register-st
                                  // alone, neutral per forward and no better in matrix-pipe utilisation: commit 926a7ad)
 static int g_attn_cross = 1;     // dp = 64, <= 128 keys: 1 = the resident-K/V cross-attention kernel, 0 = the flash loop (A/B switch)
 static int g_attn_stagger = 0;   // attn64_kernel: phase shift between the workgroups of a CU, in 64-cycle sleeps per slot (0 = off)
+// what the last cfgpp_op_attention call dispatched (host-side record, test hook): {kernel, D16, ONES, xqb}; kernel 0 = nothing
+// launched (refused), 1 = attn_kernel, 2 = attn64_kernel, 3 = xattn64_kernel; xqb = 0 for the flash kernels
+static int g_attn_last[4] = {0, 0, 0, 0};
+static void attn_note(int kernel, int d16, int ones, int xqb) {
+    g_attn_last[0] = kernel; g_attn_last[1] = d16; g_attn_last[2] = ones; g_attn_last[3] = xqb;
+}
 
 extern "C" {
 
 void cfgpp_attention_set_dma(int mode) { g_attn_dma = mode ? 1 : 0; }
 void cfgpp_attention_set_stagger(int sleeps) { g_attn_stagger = sleeps > 0 ? sleeps : 0; }
 void cfgpp_attention_set_cross(int on) { g_attn_cross = on ? 1 : 0; }
+void cfgpp_attention_last_launch(int* out4) { for (int i = 0; i < 4; ++i) out4[i] = g_attn_last[i]; }
 
 // V^T contract: when d is not a multiple of 32, row d of every [dp][tok_pad] matrix must hold ones (softmax
 // denominator through the PV MFMA).  Call once after allocating / zeroing the buffer; the QKV epilogue never
@@ -718,6 +729,7 @@ int cfgpp_op_attention_prepare_vt(void* vt, int BH, int d, int tok_pad, void* st
 // pads zero EXCEPT the ones row of vt (above).  o [B][nq][heads*d] fp16.  q_tok_pad % 128 == 0, k_tok_pad % 64 == 0.
 int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d,
                        int nq, int nk, int q_tok_pad, int k_tok_pad, void* stream) {
+    attn_note(0, 0, 0, 0);
     CFGPP_REQUIRE(q && k && vt && o, "attention: null pointer");
     CFGPP_REQUIRE(d > 0 && d <= 160 && (d % 32 == 0 || d % 8 == 0), "attention: head dim %d unsupported (multiple of 8, <= 160)", d);
     CFGPP_REQUIRE(q_tok_pad % 128 == 0 && q_tok_pad >= nq, "attention: q_tok_pad=%d (nq=%d) must be a multiple of 128", q_tok_pad, nq);
@@ -751,6 +763,7 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
         else if (ones) hipLaunchKernelGGL((xattn64_kernel<4, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb);
         else hipLaunchKernelGGL((xattn64_kernel<4, false>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb);
         CFGPP_HIP_CHECK(hipGetLastError());
+        attn_note(3, d16, ones, xqb);
         return 0;
     }
     if (dt == 2 && g_attn_dma) {                   // dp = 64 (d = 40, 48, 56, 64): LDS-DMA kernel
@@ -761,6 +774,7 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
         else rc = ones ? launch_attn64<4, true, 2, 4>(a, grid, s) : launch_attn64<4, false, 2, 4>(a, grid, s);
         if (rc) return -1;
         CFGPP_HIP_CHECK(hipGetLastError());
+        attn_note(2, d16, ones, 0);
         return 0;
     }
 #define ATTN_CASE(D16_, DT_) \
@@ -770,6 +784,7 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
     { cfgpp_set_error("attention: no kernel instance for head dim %d", d); return -2; }
 #undef ATTN_CASE
     CFGPP_HIP_CHECK(hipGetLastError());
+    attn_note(1, d16, ones, 0);
     return 0;
 }
 

@@ -65,6 +65,10 @@ void cfgpp_attention_set_stagger(int sleeps);
 /* A/B switch: 1 (default) attention with <= 128 keys and head dims padded to 64 (the 77-token cross-attention) runs the
  * resident-K/V single-pass kernel, 0 the flash loop */
 void cfgpp_attention_set_cross(int on);
+/* test hook: what the last cfgpp_op_attention call dispatched, a host-side record: out4 = {kernel (0 nothing launched: the call
+ * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
+ * from the ones row of V^T), xqb (128-query blocks per workgroup of xattn64_kernel, 0 for the flash kernels)} */
+void cfgpp_attention_last_launch(int* out4);
 int cfgpp_op_conv_in(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                      int R, int zB, int Cin, int H, int W, int Cout, void* stream);
 /* conv_in of an inpaint UNet: input channels 0..Cz-1 from z (row r % zB), Cz..Cz+Cc-1 from the fp16 condition

@@ -179,11 +179,21 @@ def make_heads(q, k, v):
     return hq, hk, hvt, q_pad, k_pad
 
 
-def attention(hq, hk, hvt, B, nheads, d, nq, nk, q_pad, k_pad):
-    o = torch.empty((B, nq, nheads * d), dtype=torch.float16, device=DEV)
+def attention(hq, hk, hvt, B, nheads, d, nq, nk, q_pad, k_pad, out=None):
+    """out: a contiguous [B, nq, nheads * d] fp16 device tensor to write into (tests that watch what the kernel leaves untouched)"""
+    o = torch.empty((B, nq, nheads * d), dtype=torch.float16, device=DEV) if out is None else out
+    assert o.is_contiguous() and o.dtype == torch.float16 and tuple(o.shape) == (B, nq, nheads * d)
     check(lib().cfgpp_op_attention(P(hq), P(hk), P(hvt), P(o), B, nheads, d, nq, nk, q_pad, k_pad, stream()),
           "cfgpp_op_attention")
     return o
+
+
+def attention_last_launch():
+    """(kernel, D16, ONES, xqb) of the last cfgpp_op_attention call (cfgpp_debug.h: cfgpp_attention_last_launch)"""
+    import ctypes
+    out4 = (ctypes.c_int * 4)()
+    lib().cfgpp_attention_last_launch(out4)
+    return tuple(out4)
 
 
 def conv_in(z, w_oihw, bias, R):
