@@ -81,6 +81,12 @@ PROTOTYPES = {
     "cfgpp_vae_device_bytes": (C.c_double, [_P]),
 }
 
+# the IP-Adapter extension header (include/cfgpp_ip_adapter.h): product entry points outside the reference's seam
+IP_ADAPTER_PROTOTYPES = {
+    "cfgpp_unet_ip_load": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_long), _I]),
+    "cfgpp_unet_image_context": (_I, [_P, _P, _I, _I, _F, _P]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_softmax_rows": (_I, [_P, _L, _I, _P]),
@@ -97,6 +103,8 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_layernorm": (_I, [_P, _P, _P, _P, _L, _I, _F, _P]),
     "cfgpp_op_attention_prepare_vt": (_I, [_P, _I, _I, _I, _P]),
     "cfgpp_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_add": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -162,7 +170,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -500,10 +500,19 @@ attn64_kernel(const AttnArgs a) {
 // LDS-DMA, the layouts of attn64_kernel) and then walks XQB blocks of 128 queries with no barrier and no running maximum: all
 // 96 scores of a query (three 32-key sub-tiles; keys >= nk_valid masked) are in registers, softmax is a single pass, and the
 // kernel is what it should be - a stream of Q in and O out.
-template <int D16, bool ONES>
+//
+// IP = true: decoupled cross-attention (IP-Adapter; diffusers IPAdapterAttnProcessor2_0).  Keys [0, nk_valid) with nk_valid <= 96
+// are the text (sub-tiles 0 - 2), keys [96, 96 + n_img) the image tokens (sub-tile 3): the same resident K / V^T, the same walk,
+// and after the text pass a SECOND complete softmax over sub-tile 3 - its own mask, maximum, fp16-rounded P, accumulators (the
+// registers of the text scores, dead by then) and denominator (the sum of its own rounded P, or the ones row of V^T met by its
+// own P; in this form the text group's denominator is summed from the rounded P as well, in the text-only form from the fp32 P) -
+//     o = fp16( O_text / l_text + ip_scale * O_img / l_img )                  one rounding, one launch.
+template <int D16, bool ONES, bool IP = false>
 __global__ void __launch_bounds__(256)
-xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, int nxb /* workgroups per batch*head */) {
+xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, int nxb /* workgroups per batch*head */,
+               int n_img /* IP: image tokens, 1 .. 32 */, float ip_scale) {
     constexpr int DP = 64, DT = 2, TILE = 64 * 128;
+    constexpr int NTXT = IP ? 3 : 4;                                   // 32-key sub-tiles the first softmax may cover
     extern __shared__ __attribute__((aligned(16))) char smem[];      // K tile 0 | V^T tile 0 | K tile 1 | V^T tile 1
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -518,7 +527,7 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
     const half_t* Qb = a.q + (long)bh * a.q_tok_pad * DP;
     const half_t* Kb = a.k + (long)bh * a.k_tok_pad * DP;
     const half_t* Vb = a.vt + (long)bh * DP * a.k_tok_pad;
-    const int ntiles = (a.nk_valid + 63) >> 6;               // 1 or 2
+    const int ntiles = IP ? 2 : (a.nk_valid + 63) >> 6;      // 1 or 2
     {
         const int r8 = lane >> 3, pc = lane & 7;
 #pragma unroll
@@ -559,9 +568,9 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
 #pragma unroll
         for (int ks = 0; ks < D16; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(Qb + (long)(q0n + l31) * DP + ks * 16 + hi * 8);
         // ---- S^T = K Q^T for up to four 32-key sub-tiles ----
-        f32x16 s[4];
+        f32x16 s[NTXT];
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 0; st < NTXT; ++st) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) s[st][r] = 0.f;
             if (st < nsub) {
@@ -576,7 +585,7 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
         // ---- softmax over all keys at once (log2 domain); keys >= nk_valid masked ----
         float mx = -INFINITY;
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 0; st < NTXT; ++st) {
             if (st < nsub) {
                 if (st == nsub - 1 && (a.nk_valid & 31) != 0) {      // (wave-uniform) only the last sub-tile has invalid keys
                     const int nv = (a.nk_valid & 31) - 4 * hi;         // valid keys of this sub-tile, seen from this half-wave
@@ -590,13 +599,13 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         float psum = 0.f;
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 0; st < NTXT; ++st) {
             if (st < nsub) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const float pv = __builtin_amdgcn_exp2f(s[st][r] - mx);
                     s[st][r] = pv;
-                    if constexpr (!ONES) psum += pv;
+                    if constexpr (!ONES) psum += IP ? (float)(half_t)pv : pv;     // IP form: the denominator of the P the MFMAs see
                 }
             }
         }
@@ -607,7 +616,7 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
 #pragma unroll
             for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
 #pragma unroll
-        for (int st = 0; st < 4; ++st) {
+        for (int st = 0; st < NTXT; ++st) {
             if (st < nsub) {
                 const char* Vs = smem + (st >> 1) * 2 * TILE + TILE;
 #pragma unroll
@@ -635,6 +644,72 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
             l_tot = psum + __shfl_xor(psum, 32);
         }
         const float inv_l = 1.0f / l_tot;
+        if constexpr (IP) {
+            // ---- the image keys: sub-tile 3 = rows 32 .. 63 of K tile 1, columns 32 .. 63 of V^T tile 1 ----
+            __builtin_amdgcn_sched_barrier(0);       // the text pass is over: its score registers are free for what follows
+            f32x16 si;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) si[r] = 0.f;
+            {
+                const char* Ks = smem + 2 * TILE + 32 * 128;
+#pragma unroll
+                for (int ks = 0; ks < D16; ++ks) {
+                    const half8_t kf = *reinterpret_cast<const half8_t*>(Ks + frow + ((((ks << 1) | hi) ^ fsw) << 4));
+                    si = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qs[ks], si, 0, 0, 0);
+                }
+            }
+            if (n_img < 32) {                                          // (wave-uniform)
+                const int nv = n_img - 4 * hi;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) si[r] = ((r & 3) + 8 * (r >> 2)) < nv ? si[r] : -INFINITY;
+            }
+            float mi = si[0];
+#pragma unroll
+            for (int r = 1; r < 16; ++r) mi = fmaxf(mi, si[r]);
+            mi = fmaxf(mi, __shfl_xor(mi, 32));
+            float pisum = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float pv = __builtin_amdgcn_exp2f(si[r] - mi);
+                si[r] = pv;
+                if constexpr (!ONES) pisum += (float)(half_t)pv;
+            }
+            f32x16 oi[DT];
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oi[i][r] = 0.f;
+            {
+                const char* Vs = smem + 2 * TILE + TILE;
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) {
+                    half8_t pf;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pf[j] = (half_t)si[8 * tt + j];
+                    const int lc = 4 + 2 * tt + hi;
+#pragma unroll
+                    for (int i = 0; i < DT; ++i) {
+                        const half8_t vf = *reinterpret_cast<const half8_t*>(Vs + i * 32 * 128 + frow + ((lc ^ fsw) << 4));
+                        oi[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oi[i], 0, 0, 0);
+                    }
+                }
+            }
+            float li;
+            if constexpr (ONES) {
+                const int dr = a.d & 31;
+                float lv = 0.f;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) if (dr == 8 * g) lv = oi[DT - 1][4 * g];
+                li = __shfl(lv, l31);
+            } else {
+                li = pisum + __shfl_xor(pisum, 32);
+            }
+            const float wi = ip_scale / li;
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) oacc[i][r] = oacc[i][r] * inv_l + wi * oi[i][r];
+        }
         if (qrow < a.nq) {
             half_t* orow = a.o + ((long)b * a.nq + qrow) * a.o_ld + head * a.d;
 #pragma unroll
@@ -645,7 +720,7 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
                     if (dd < a.d) {
                         half4_t o;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = (half_t)(oacc[i][4 * g + k] * inv_l);
+                        for (int k = 0; k < 4; ++k) o[k] = (half_t)(IP ? oacc[i][4 * g + k] : oacc[i][4 * g + k] * inv_l);
                         *reinterpret_cast<half4_t*>(orow + dd) = o;
                     }
                 }
@@ -675,6 +750,79 @@ __global__ void attn_ones_row_kernel(half_t* vt, int BH, int d, int dp, int tok_
     vt[(bh * dp + d) * tok_pad + k] = (half_t)1.0f;
 }
 
+// Image branch of the decoupled cross-attention for the head dims without a fused instance (dp != 64: SD1.5's d = 80 / 160, the tiny
+// nets' d = 32; correctness path).  o already holds fp16(O_text) from a launch of the kernels above over the text keys; one thread
+// per (batch*head, query) runs the complete softmax over the image keys [96, 96 + n_img) in fp32 with the rounding points of the
+// MFMA kernels (q * d^-1/2 * log2(e) to fp16, P to fp16, the denominator summed from the rounded P) and stores
+//     o = fp16( float(o) + ip_scale * O_img / l_img ).
+// K rows / V^T columns are the same for every thread of a block (uniform loads); n_img <= 32 scores live in registers.
+__global__ void __launch_bounds__(256)
+attn_ip_add_kernel(const AttnArgs a, int dp, int n_img, float ip_scale) {
+    const int q = blockIdx.x * 256 + threadIdx.x, bh = blockIdx.y;
+    if (q >= a.nq) return;
+    const half_t* Qr = a.q + ((long)bh * a.q_tok_pad + q) * dp;
+    const half_t* Ki = a.k + ((long)bh * a.k_tok_pad + 96) * dp;
+    const half_t* Vi = a.vt + (long)bh * dp * a.k_tok_pad + 96;
+    float sc[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) sc[k] = 0.f;
+    for (int d0 = 0; d0 < a.d; d0 += 8) {
+        const half8_t raw = *reinterpret_cast<const half8_t*>(Qr + d0);
+        float qs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qs[j] = (float)(half_t)((float)raw[j] * a.scale_log2e);
+#pragma unroll
+        for (int k = 0; k < 32; ++k)
+            if (k < n_img) {
+                const half8_t kf = *reinterpret_cast<const half8_t*>(Ki + (long)k * dp + d0);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) sc[k] += qs[j] * (float)kf[j];
+            }
+    }
+    float m = sc[0];
+#pragma unroll
+    for (int k = 1; k < 32; ++k) if (k < n_img) m = fmaxf(m, sc[k]);
+    float l = 0.f;
+#pragma unroll
+    for (int k = 0; k < 32; ++k) {
+        sc[k] = k < n_img ? (float)(half_t)__builtin_amdgcn_exp2f(sc[k] - m) : 0.f;
+        l += sc[k];
+    }
+    const float wi = ip_scale / l;
+    const int b = bh / a.heads, head = bh - b * a.heads;
+    half_t* orow = a.o + ((long)b * a.nq + q) * a.o_ld + head * a.d;
+    for (int d0 = 0; d0 < a.d; d0 += 4) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 32; ++k)
+            if (k < n_img) {
+                const int col = cfgpp_vt_pos(k);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[j] += sc[k] * (float)Vi[(long)(d0 + j) * a.k_tok_pad + col];
+            }
+        half4_t o = *reinterpret_cast<const half4_t*>(orow + d0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (half_t)((float)o[j] + wi * acc[j]);
+        *reinterpret_cast<half4_t*>(orow + d0) = o;
+    }
+}
+
+// zeroes key slots [slot0, slot0 + n) of every K matrix (all dp columns) and of rows < d of every V^T matrix - the ones row (row d)
+// and the zero rows above it stay as they are.  One thread per (bh, 8 halfs): slot0, n and tok_pad are multiples of 8.
+__global__ void attn_clear_slots_kernel(half_t* k, half_t* vt, int BH, int d, int dp, int tok_pad, int slot0, int n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long per_k = (long)n * dp / 8, per_v = (long)d * n / 8;
+    if (i >= (long)BH * (per_k + per_v)) return;
+    const long bh = i / (per_k + per_v), r = i - bh * (per_k + per_v);
+    const half8_t z = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (r < per_k) {
+        *reinterpret_cast<half8_t*>(k + (bh * tok_pad + slot0) * dp + r * 8) = z;
+    } else {
+        const long e = r - per_k, row = e / (n / 8), c = e - row * (n / 8);
+        *reinterpret_cast<half8_t*>(vt + (bh * dp + row) * tok_pad + slot0 + c * 8) = z;
+    }
+}
+
 template <int D16, int DT, bool ONES, int QT>
 int launch_attn(const AttnArgs& a, dim3 grid, hipStream_t s) {
     constexpr int DP = DT * 32;
@@ -698,8 +846,9 @@ static int g_attn_dma = 1;       // dp = 64: 1 = LDS-DMA kernel, 0 = register-st
                                  // alone, neutral per forward and no better in matrix-pipe utilisation: commit 926a7ad)
 static int g_attn_cross = 1;     // dp = 64, <= 128 keys: 1 = the resident-K/V cross-attention kernel, 0 = the flash loop (A/B switch)
 static int g_attn_stagger = 0;   // attn64_kernel: phase shift between the workgroups of a CU, in 64-cycle sleeps per slot (0 = off)
-// what the last cfgpp_op_attention call dispatched (host-side record, test hook): {kernel, D16, ONES, xqb}; kernel 0 = nothing
-// launched (refused), 1 = attn_kernel, 2 = attn64_kernel, 3 = xattn64_kernel; xqb = 0 for the flash kernels
+// what the last cfgpp_op_attention / cfgpp_op_attention_ip call dispatched (host-side record, test hook): {kernel, D16, ONES, xqb};
+// kernel 0 = nothing launched (refused), 1 = attn_kernel, 2 = attn64_kernel, 3 = xattn64_kernel, 4 = xattn64_kernel IP form,
+// 5 = attn_ip_add_kernel (the last launch of the two-pass form); xqb = 0 for the flash kernels and for 5
 static int g_attn_last[4] = {0, 0, 0, 0};
 static void attn_note(int kernel, int d16, int ones, int xqb) {
     g_attn_last[0] = kernel; g_attn_last[1] = d16; g_attn_last[2] = ones; g_attn_last[3] = xqb;
@@ -721,6 +870,19 @@ int cfgpp_op_attention_prepare_vt(void* vt, int BH, int d, int tok_pad, void* st
     CFGPP_REQUIRE(d % 8 == 0, "attention: head dim %d (not a multiple of 32) must be a multiple of 8", d);
     const int dp = (d + 31) / 32 * 32;
     hipLaunchKernelGGL(attn_ones_row_kernel, dim3(cdiv((long)BH * tok_pad, 256)), dim3(256), 0, (hipStream_t)stream, (half_t*)vt, BH, d, dp, tok_pad);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Zero the key slots [slot0, slot0 + n) of k [BH][tok_pad][dp] and vt [BH][dp][tok_pad] without touching the ones row of vt (the
+// image-token slots of the cross-attention buffers, before a new set of image tokens is projected into them).
+int cfgpp_op_attention_clear_slots(void* k, void* vt, int BH, int d, int tok_pad, int slot0, int n, void* stream) {
+    CFGPP_REQUIRE(k && vt && BH > 0 && d > 0 && d % 8 == 0, "attention_clear_slots: bad args (d=%d)", d);
+    CFGPP_REQUIRE(slot0 >= 0 && n > 0 && slot0 % 8 == 0 && n % 8 == 0 && tok_pad % 8 == 0 && slot0 + n <= tok_pad,
+                  "attention_clear_slots: slots [%d, %d) of %d (multiples of 8)", slot0, slot0 + n, tok_pad);
+    const int dp = (d + 31) / 32 * 32;
+    const long total = (long)BH * ((long)n * dp / 8 + (long)d * n / 8);
+    hipLaunchKernelGGL(attn_clear_slots_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (half_t*)k, (half_t*)vt, BH, d, dp, tok_pad, slot0, n);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -759,9 +921,9 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
             attr_set = true;
         }
         const dim3 xg(BH * nxb);
-        if (d16 == 3) hipLaunchKernelGGL((xattn64_kernel<3, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb);
-        else if (ones) hipLaunchKernelGGL((xattn64_kernel<4, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb);
-        else hipLaunchKernelGGL((xattn64_kernel<4, false>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb);
+        if (d16 == 3) hipLaunchKernelGGL((xattn64_kernel<3, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, 0, 0.f);
+        else if (ones) hipLaunchKernelGGL((xattn64_kernel<4, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, 0, 0.f);
+        else hipLaunchKernelGGL((xattn64_kernel<4, false>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, 0, 0.f);
         CFGPP_HIP_CHECK(hipGetLastError());
         attn_note(3, d16, ones, xqb);
         return 0;
@@ -785,6 +947,60 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
 #undef ATTN_CASE
     CFGPP_HIP_CHECK(hipGetLastError());
     attn_note(1, d16, ones, 0);
+    return 0;
+}
+
+// Decoupled cross-attention (IP-Adapter): o = fp16( softmax(q K_text) V_text + ip_scale * softmax(q K_img) V_img ).  Buffers as
+// cfgpp_op_attention with k_tok_pad >= 128: keys [0, nk_text), nk_text <= 96, are the text, keys [96, 96 + n_img), n_img <= 32, the
+// image tokens; every other slot is a pad that enters neither softmax.  The V^T permutation and the ones row hold for the image
+// columns as for the text ones.  dp = 64 with the default switches: ONE launch of xattn64_kernel<.., IP = true> (record: kernel 4).
+// Every other head dim, or dp = 64 under cfgpp_attention_set_dma(0) / set_cross(0): cfgpp_op_attention over the text keys (O_text
+// rounded to fp16), then attn_ip_add_kernel (record: kernel 5).  ip_scale == 0 is the text-only call: cfgpp_op_attention, its record.
+int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int nk_text,
+                          int n_img, float ip_scale, int q_tok_pad, int k_tok_pad, void* stream) {
+    attn_note(0, 0, 0, 0);
+    CFGPP_REQUIRE(q && k && vt && o, "attention_ip: null pointer");
+    CFGPP_REQUIRE(B > 0 && heads > 0 && nq > 0, "attention_ip: B=%d heads=%d nq=%d", B, heads, nq);
+    CFGPP_REQUIRE(nk_text >= 1 && nk_text <= 96, "attention_ip: nk_text=%d (1 .. 96 text keys; the image keys start at slot 96)", nk_text);
+    CFGPP_REQUIRE(n_img >= 1 && n_img <= 32, "attention_ip: n_img=%d (1 .. 32 image tokens)", n_img);
+    CFGPP_REQUIRE(k_tok_pad >= 128 && k_tok_pad % 64 == 0, "attention_ip: k_tok_pad=%d must be a multiple of 64 and >= 128", k_tok_pad);
+    CFGPP_REQUIRE(d > 0 && d <= 160 && d % 8 == 0, "attention_ip: head dim %d unsupported (multiple of 8, <= 160)", d);
+    CFGPP_REQUIRE(q_tok_pad % 128 == 0 && q_tok_pad >= nq, "attention_ip: q_tok_pad=%d (nq=%d) must be a multiple of 128", q_tok_pad, nq);
+    if (ip_scale == 0.f) return cfgpp_op_attention(q, k, vt, o, B, heads, d, nq, nk_text, q_tok_pad, k_tok_pad, stream);
+    AttnArgs a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.o = (half_t*)o;
+    a.heads = heads; a.d = d; a.nq = nq; a.nk_valid = nk_text; a.q_tok_pad = q_tok_pad; a.k_tok_pad = k_tok_pad;
+    a.o_ld = heads * d;
+    a.scale_log2e = (1.0f / sqrtf((float)d)) * 1.4426950408889634f;
+    a.nqb = cdiv(nq, 128);
+    a.stagger = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int d16 = (d + 15) / 16, dt = (d + 31) / 32, BH = B * heads;
+    const bool ones = (d % 32) != 0;
+    if (dt == 2 && g_attn_dma && g_attn_cross) {
+        int xqb = 1;        // the walk of cfgpp_op_attention's cross-attention branch
+        while (xqb < 8 && a.nqb % (xqb * 2) == 0 && (long)BH * (a.nqb / (xqb * 2)) >= 512) xqb *= 2;
+        const int nxb = a.nqb / xqb;
+        static bool attr_set = false;
+        if (!attr_set) {
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_kernel<3, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128));
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_kernel<4, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128));
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_kernel<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 64 * 128));
+            attr_set = true;
+        }
+        const dim3 xg(BH * nxb);
+        if (d16 == 3) hipLaunchKernelGGL((xattn64_kernel<3, true, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, n_img, ip_scale);
+        else if (ones) hipLaunchKernelGGL((xattn64_kernel<4, true, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, n_img, ip_scale);
+        else hipLaunchKernelGGL((xattn64_kernel<4, false, true>), xg, dim3(256), 4 * 64 * 128, s, a, xqb, nxb, n_img, ip_scale);
+        CFGPP_HIP_CHECK(hipGetLastError());
+        attn_note(4, d16, ones, xqb);
+        return 0;
+    }
+    int e = cfgpp_op_attention(q, k, vt, o, B, heads, d, nq, nk_text, q_tok_pad, k_tok_pad, stream);
+    if (e) return e;
+    hipLaunchKernelGGL(attn_ip_add_kernel, dim3(cdiv(nq, 256), BH), dim3(256), 0, s, a, dt * 32, n_img, ip_scale);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    attn_note(5, d16, ones, 0);
     return 0;
 }
 

@@ -66,9 +66,20 @@ void cfgpp_attention_set_stagger(int sleeps);
  * resident-K/V single-pass kernel, 0 the flash loop */
 void cfgpp_attention_set_cross(int on);
 /* test hook: what the last cfgpp_op_attention call dispatched, a host-side record: out4 = {kernel (0 nothing launched: the call
- * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
+ * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
  * from the ones row of V^T), xqb (128-query blocks per workgroup of xattn64_kernel, 0 for the flash kernels)} */
 void cfgpp_attention_last_launch(int* out4);
+/* zero key slots [slot0, slot0 + n) of k [BH][tok_pad][dp] and of rows < d of vt [BH][dp][tok_pad] (the ones row stays) */
+int cfgpp_op_attention_clear_slots(void* k, void* vt, int BH, int d, int tok_pad, int slot0, int n, void* stream);
+/* Decoupled cross-attention of an IP-Adapter (diffusers IPAdapterAttnProcessor2_0.__call__: a second SDPA call over the image
+ * tokens and `hidden_states + scale * ip_hidden_states`): o = fp16(softmax(q K_text) V_text + ip_scale * softmax(q K_img) V_img).
+ * Buffers as cfgpp_op_attention, k_tok_pad >= 128: keys [0, nk_text) (nk_text <= 96) are text, keys [96, 96 + n_img)
+ * (1 <= n_img <= 32) image tokens, all other slots pads that enter neither softmax; V^T permutation and ones row as above.
+ * Head dims padded to 64: one launch (last_launch kernel 4 = xattn64_kernel, IP form).  Other head dims, or the A/B switches off:
+ * cfgpp_op_attention over the text keys, then the image branch added in a second launch (kernel 5), rounding O_text to fp16
+ * in between.  ip_scale == 0: the text-only call.  Refused, nothing launched: nk_text > 96, n_img > 32, k_tok_pad < 128. */
+int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int nk_text,
+                          int n_img, float ip_scale, int q_tok_pad, int k_tok_pad, void* stream);
 int cfgpp_op_conv_in(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                      int R, int zB, int Cin, int H, int W, int Cout, void* stream);
 /* conv_in of an inpaint UNet: input channels 0..Cz-1 from z (row r % zB), Cz..Cz+Cc-1 from the fp16 condition

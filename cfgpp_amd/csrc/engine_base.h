@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/cfgpp.h"
+#include "../../include/cfgpp_ip_adapter.h"
 #include "cfgpp_debug.h"
 #include "igemm.h"
 

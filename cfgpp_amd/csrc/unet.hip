@@ -26,7 +26,8 @@ struct cfgpp_unet : EngineBase {
     // whole-step graph replay (cfgpp_sample_graph_ddim): per-step scalar table, current-step block, step counter, the one cached graph
     float* d_step_tab = nullptr; int step_tab_cap = 0; float* d_step_cur = nullptr; int* d_step_idx = nullptr;
     hipStream_t cap_stream = nullptr;
-    struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; int cond_rows; };
+    struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; int cond_rows;
+                      int ip_active = 0, ip_n_img = 0; unsigned ip_scale_bits = 0; };      // the adapter state the captured launches baked in
     struct Graph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<Graph> graphs;              // most recently used last; at most 4 (an invert + edit job alternates between two)
     int tuned_serial = 0;                   // bumps whenever the pins of the current batch change (a graph bakes the tiles it captured)
@@ -47,7 +48,7 @@ struct cfgpp_unet : EngineBase {
     }
     static void destroy(Graph& g) { if (g.exec) hipGraphExecDestroy(g.exec); if (g.graph) hipGraphDestroy(g.graph); g.exec = nullptr; g.graph = nullptr; }
     void drop_graphs() { for (auto& g : graphs) destroy(g); graphs.clear(); }
-    ~cfgpp_unet() { drop_graphs(); if (cap_stream) hipStreamDestroy(cap_stream); }
+    ~cfgpp_unet() { drop_graphs(); if (cap_stream) hipStreamDestroy(cap_stream); for (auto& a : ip_allocs) hipFree(a.first); }
     // context inputs
     const half_t* ctx_ehs = nullptr; int ctx_rows = 0; int ctx_tokens = 77;
     const half_t* ctx_text = nullptr; const float* ctx_tids = nullptr; int ctx_cond_rows = 0;
@@ -77,6 +78,54 @@ struct cfgpp_unet : EngineBase {
     std::vector<Tensor> ctrl_dst;
     cfgpp_unet* ctrl = nullptr; float ctrl_scale = 0.f;
     CnAddEntry* d_ctrl_tab = nullptr; long ctrl_max_n8 = 0;
+
+    // ---- IP-Adapter (cfgpp_unet_ip_load / cfgpp_unet_image_context).  Every cross-attention block keeps its text K / V^T in
+    // key slots [0, 77) of ck / cvt (ck_pad = 128 slots); the image tokens' K / V^T go into slots [96, 96 + n_img) of the same
+    // buffers and the block's attention op becomes the decoupled form while the adapter is active.
+    static constexpr int IP_SLOT = 96, IP_MAX = 32;
+    struct IpBlock {
+        std::string name;               // "<diffusers block>.attn2"
+        int C, nheads, d, dp, tok; half_t* ck; half_t* cvt;
+        size_t plan_idx;                // the block's cross-attention op in `plan`
+        half_t* wkv = nullptr;          // [to_k_ip ; to_v_ip] = [2C][cross_dim] fp16 (adapter memory)
+        bool has_k = false, has_v = false;
+    };
+    std::vector<IpBlock> ip_blocks;     // plan order
+    int ip_ck_pad = 0;
+    half_t* ip_wproj = nullptr; float* ip_bproj = nullptr; float* ip_ng = nullptr; float* ip_nb = nullptr;
+    long ip_proj_rows = 0, ip_bias_rows = 0; int ip_embed = 0;      // image_proj.proj: [n_img * cross_dim][embed_dim]
+    half_t* ip_proj_out = nullptr; half_t* ip_tok = nullptr; long ip_tok_cap = 0;   // proj output / LayerNorm output, [rows][n_img][cross_dim]
+    std::vector<std::pair<void*, size_t>> ip_allocs;
+    bool ip_active = false; int ip_n_img = 0; float ip_scale = 0.f;
+    const void* ip_src = nullptr; int ip_rows = 0;                  // the embeds the slots were computed from (by address) and their rows
+    void* ip_malloc(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
+        ip_allocs.push_back(std::make_pair(p, bytes)); dev_bytes += (double)bytes;
+        return p;
+    }
+    void ip_free(void* p) {
+        for (size_t i = 0; i < ip_allocs.size(); ++i)
+            if (ip_allocs[i].first == p) { hipFree(p); dev_bytes -= (double)ip_allocs[i].second; ip_allocs.erase(ip_allocs.begin() + i); return; }
+    }
+    // the image keys count in the FLOPs and in the profiler's tags only while the adapter is active
+    double ip_macs_per_key = 0;         // sum over blocks of 2 * heads * tokens * d
+    void ip_set_active(bool on, int n_img, float scale) {
+        ip_active = on; ip_n_img = on ? n_img : 0; ip_scale = on ? scale : 0.f;
+        for (const IpBlock& b : ip_blocks) {
+            const double per_key = 2.0 * (double)b.nheads * b.tok * b.d;
+            const std::string desc = "cross_attn heads=" + std::to_string(b.nheads) + " N=" + std::to_string(b.tok) + " d=" + std::to_string(b.d);
+            plan_macs[b.plan_idx] = per_key * (77 + ip_n_img);
+            plan_desc[b.plan_idx] = on ? desc + " ip=" + std::to_string(n_img) : desc;
+        }
+    }
+    void ip_drop() {
+        if (plan_macs.size() == plan.size()) ip_set_active(false, 0, 0.f);
+        while (!ip_allocs.empty()) ip_free(ip_allocs.back().first);
+        for (IpBlock& b : ip_blocks) { b.wkv = nullptr; b.has_k = b.has_v = false; }
+        ip_wproj = nullptr; ip_bproj = nullptr; ip_ng = nullptr; ip_nb = nullptr; ip_proj_out = nullptr; ip_tok = nullptr;
+        ip_proj_rows = ip_bias_rows = 0; ip_embed = 0; ip_tok_cap = 0; ip_src = nullptr; ip_rows = 0;
+    }
 };
 
 static int g_share_prefix = 1;
@@ -522,6 +571,8 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                 });
             }
             ++cross_block_counter;
+            u->ip_ck_pad = ck_pad;
+            u->ip_blocks.push_back(cfgpp_unet::IpBlock{b + ".attn2", C, nheads, d, dp, tok, ck, cvt, 0});
             // self-attention
             P.layernorm(u->tok_x, u->tok_ln, l1g, l1b, tok, C);
             P.heads(u->tok_ln, C, wqkv, 3 * C, tok, 0, C, nheads, HQ, HK, HVT, q_pad, k_pad);
@@ -554,8 +605,13 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                 u->attn_macs_per_row += 2.0 * (double)nheads * tok * 77 * d;
                 half_t* hq = HQ; half_t* o = u->tok_attn;
                 u->plan.push_back([=](hipStream_t s, int rows) {
+                    if (uu->ip_active)      // IP-Adapter: text + image keys in ONE launch (head dims padded to 64), same launch count
+                        return cfgpp_op_attention_ip(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, uu->ip_n_img, uu->ip_scale, q_pad,
+                                                     ck_pad, s);
                     return cfgpp_op_attention(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, q_pad, ck_pad, s);
                 });
+                u->ip_blocks.back().plan_idx = u->plan.size() - 1;
+                u->ip_macs_per_key += 2.0 * (double)nheads * tok * d;
                 u->tag(1, 2.0 * (double)nheads * tok * 77 * d, "cross_attn heads=" + std::to_string(nheads) + " N=" + std::to_string(tok) + " d=" + std::to_string(d));
             }
             P.linear(u->tok_attn, C, u->tok_x, C, wo2, bo2, u->tok_x, tok);
@@ -747,6 +803,167 @@ int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, v
     return 0;
 }
 
+// ---- IP-Adapter ------------------------------------------------------------------------------------------------------------
+// diffusers `load_ip_adapter` for the non-"plus" adapters (ip-adapter_sd15, ip-adapter_sdxl, ip-adapter_sdxl_vit-h):
+// `unet.encoder_hid_proj` = ImageProjection (Linear embed_dim -> n_img * cross_dim, reshape, LayerNorm) and one
+// IPAdapterAttnProcessor2_0 per cross-attention with its own to_k_ip / to_v_ip.  No reference counterpart.
+static int ip_fail(const char* key, const char* why) { cfgpp_set_error("ip_load: %s: %s", key, why); return -2; }
+
+int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dtype, const long* shape, int ndim) {
+    CFGPP_REQUIRE(u && u->finalized, "ip_load: the engine is not finalized (the adapter attaches to the uploaded UNet)");
+    CFGPP_REQUIRE(!u->control, "ip_load: a ControlNet takes no image tokens (diffusers passes it the text context only)");
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    if (!key) {                 // drop the adapter
+        CFGPP_HIP_CHECK(hipDeviceSynchronize());        // an earlier forward may still read its K / V^T slots
+        u->ip_drop();
+        for (const auto& b : u->ip_blocks)
+            if (cfgpp_op_attention_clear_slots(b.ck, b.cvt, u->max_rows * b.nheads, b.d, u->ip_ck_pad, cfgpp_unet::IP_SLOT, cfgpp_unet::IP_MAX, nullptr)) return -1;
+        return 0;
+    }
+    CFGPP_REQUIRE(host && shape && (dtype == 0 || dtype == 1), "ip_load: %s: null tensor or dtype %d (0 fp32, 1 fp16)", key, dtype);
+    const std::string k = key;
+    const long cross = u->cfg.cross_attention_dim;
+    long n = 1; for (int i = 0; i < ndim; ++i) n *= shape[i];
+    auto to_half = [&](std::vector<half_t>& h) {
+        h.resize(n);
+        if (dtype == 0) { const float* s = (const float*)host; for (long i = 0; i < n; ++i) h[i] = (half_t)s[i]; }
+        else std::memcpy(h.data(), host, n * sizeof(half_t));
+    };
+    auto to_float = [&](std::vector<float>& f) {
+        f.resize(n);
+        if (dtype == 0) std::memcpy(f.data(), host, n * sizeof(float));
+        else { const half_t* s = (const half_t*)host; for (long i = 0; i < n; ++i) f[i] = (float)s[i]; }
+    };
+    // a tensor that replaces an earlier one is uploaded first and swapped in after: a failed call changes nothing
+    auto put = [&](void** slot, const void* data, size_t bytes) {
+        void* d = u->ip_malloc(bytes);
+        if (!d) return ip_fail(key, "out of device memory");
+        if (hipMemcpy(d, data, bytes, hipMemcpyHostToDevice) != hipSuccess) { u->ip_free(d); return ip_fail(key, "hipMemcpy failed"); }
+        if (*slot) { hipDeviceSynchronize(); u->ip_free(*slot); }
+        *slot = d;
+        return 0;
+    };
+    auto changed = [&]() { if (u->ip_active) u->ip_set_active(false, 0, 0.f); u->ip_src = nullptr; };      // the slots are stale now
+    if (k == "image_proj.proj.weight") {
+        if (ndim != 2 || shape[0] % cross != 0 || shape[0] / cross < 1 || shape[0] / cross > cfgpp_unet::IP_MAX || shape[1] < 64 || shape[1] % 64 != 0) {
+            cfgpp_set_error("ip_load: %s: shape [%ld, %ld], expected [n_img * %ld, embed_dim] with 1 <= n_img <= %d image tokens and embed_dim a "
+                            "multiple of 64", key, ndim > 0 ? shape[0] : 0, ndim > 1 ? shape[1] : 0, cross, cfgpp_unet::IP_MAX);
+            return -2;
+        }
+        std::vector<half_t> h; to_half(h);
+        if (int e = put((void**)&u->ip_wproj, h.data(), h.size() * sizeof(half_t))) return e;
+        u->ip_proj_rows = shape[0]; u->ip_embed = (int)shape[1];
+        changed();
+        return 0;
+    }
+    if (k == "image_proj.proj.bias") {
+        if (ndim != 1 || shape[0] % cross != 0 || shape[0] / cross < 1 || shape[0] / cross > cfgpp_unet::IP_MAX) {
+            cfgpp_set_error("ip_load: %s: %ld elements, expected n_img * %ld with 1 <= n_img <= %d", key, n, cross, cfgpp_unet::IP_MAX); return -2;
+        }
+        std::vector<float> f; to_float(f);
+        if (int e = put((void**)&u->ip_bproj, f.data(), f.size() * sizeof(float))) return e;
+        u->ip_bias_rows = shape[0];
+        changed();
+        return 0;
+    }
+    if (k == "image_proj.norm.weight" || k == "image_proj.norm.bias") {
+        if (ndim != 1 || shape[0] != cross) { cfgpp_set_error("ip_load: %s: %ld elements, expected cross_attention_dim = %ld", key, n, cross); return -2; }
+        std::vector<float> f; to_float(f);
+        if (int e = put((void**)(k == "image_proj.norm.weight" ? &u->ip_ng : &u->ip_nb), f.data(), f.size() * sizeof(float))) return e;
+        changed();
+        return 0;
+    }
+    for (int part = 0; part < 2; ++part) {
+        const std::string suf = part == 0 ? ".to_k_ip.weight" : ".to_v_ip.weight";
+        if (k.size() <= suf.size() || k.compare(k.size() - suf.size(), suf.size(), suf) != 0) continue;
+        const std::string blk = k.substr(0, k.size() - suf.size());
+        for (auto& b : u->ip_blocks) {
+            if (b.name != blk) continue;
+            if (ndim != 2 || shape[0] != b.C || shape[1] != cross) {
+                cfgpp_set_error("ip_load: %s: shape [%ld, %ld], expected [%d, %ld]", key, ndim > 0 ? shape[0] : 0, ndim > 1 ? shape[1] : 0, b.C, cross);
+                return -2;
+            }
+            if (!b.wkv) {
+                b.wkv = (half_t*)u->ip_malloc((size_t)2 * b.C * cross * sizeof(half_t));
+                if (!b.wkv) return ip_fail(key, "out of device memory");
+                CFGPP_HIP_CHECK(hipMemset(b.wkv, 0, (size_t)2 * b.C * cross * sizeof(half_t)));
+            }
+            std::vector<half_t> h; to_half(h);
+            CFGPP_HIP_CHECK(hipDeviceSynchronize());
+            CFGPP_HIP_CHECK(hipMemcpy(b.wkv + (size_t)part * b.C * cross, h.data(), h.size() * sizeof(half_t), hipMemcpyHostToDevice));
+            (part == 0 ? b.has_k : b.has_v) = true;
+            changed();
+            return 0;
+        }
+    }
+    cfgpp_set_error("ip_load: unknown key %s (image_proj.proj.{weight,bias}, image_proj.norm.{weight,bias}, <transformer block>.attn2.to_k_ip.weight / "
+                    ".to_v_ip.weight)", key);
+    return -3;
+}
+
+// Replaces, per job instead of per step and per block: `image_embeds = self.encoder_hid_proj(image_embeds)` (ImageProjection.forward)
+// of UNet2DConditionModel.process_encoder_hidden_states and `ip_key = self.to_k_ip[i](ip_hidden_states)` / `ip_value = ...` of
+// IPAdapterAttnProcessor2_0.__call__; the per-step part (second SDPA + `hidden_states + scale * ip_hidden_states`) is the attention
+// op of the plan.  No reference counterpart.
+int cfgpp_unet_image_context(cfgpp_unet* u, const void* image_embeds, int rows, int embed_dim, float scale, void* stream) {
+    CFGPP_REQUIRE(u && u->finalized, "image_context: engine not finalized");
+    CFGPP_REQUIRE(!u->control, "image_context: a ControlNet takes no image tokens");
+    if (!image_embeds || scale == 0.f) {            // deactivate: the next forward is the text-only plan, launch for launch
+        if (u->ip_active) u->ip_set_active(false, 0, 0.f);
+        return 0;
+    }
+    {
+        std::string miss; int nm = 0;
+        auto need = [&](bool have, const std::string& name) { if (!have) { if (nm < 8) miss += name + " "; ++nm; } };
+        need(u->ip_wproj, "image_proj.proj.weight"); need(u->ip_bproj, "image_proj.proj.bias");
+        need(u->ip_ng, "image_proj.norm.weight"); need(u->ip_nb, "image_proj.norm.bias");
+        for (const auto& b : u->ip_blocks) { need(b.has_k, b.name + ".to_k_ip.weight"); need(b.has_v, b.name + ".to_v_ip.weight"); }
+        if (nm) { cfgpp_set_error("image_context: missing %d adapter tensors (cfgpp_unet_ip_load): %s%s", nm, miss.c_str(), nm > 8 ? "..." : ""); return -2; }
+    }
+    CFGPP_REQUIRE(u->ip_bias_rows == u->ip_proj_rows, "image_context: image_proj.proj.bias has %ld elements, image_proj.proj.weight %ld rows",
+                  u->ip_bias_rows, u->ip_proj_rows);
+    CFGPP_REQUIRE(embed_dim == u->ip_embed, "image_context: embed_dim=%d, the adapter's image_proj.proj takes %d", embed_dim, u->ip_embed);
+    CFGPP_REQUIRE(u->ctx_set && rows == u->ctx_rows, "image_context: rows=%d must equal the rows of the current text context (%d): call "
+                  "cfgpp_unet_set_context first", rows, u->ctx_set ? u->ctx_rows : 0);
+    const int cross = u->cfg.cross_attention_dim, n_img = (int)(u->ip_proj_rows / cross);
+    hipStream_t s = (hipStream_t)stream;
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    if (!(u->ip_src == image_embeds && u->ip_rows == rows)) {       // (a new scale alone keeps the projected K / V^T)
+        const long need_el = (long)u->max_rows * n_img * cross;
+        if (u->ip_tok_cap < need_el) {
+            CFGPP_HIP_CHECK(hipDeviceSynchronize());
+            if (u->ip_proj_out) u->ip_free(u->ip_proj_out);
+            if (u->ip_tok) u->ip_free(u->ip_tok);
+            u->ip_proj_out = (half_t*)u->ip_malloc((size_t)need_el * sizeof(half_t));
+            u->ip_tok = (half_t*)u->ip_malloc((size_t)need_el * sizeof(half_t));
+            u->ip_tok_cap = (u->ip_proj_out && u->ip_tok) ? need_el : 0;
+            CFGPP_REQUIRE(u->ip_tok_cap, "image_context: out of device memory");
+        }
+        u->ip_src = nullptr;
+        {   // tokens = LayerNorm(reshape(proj(embeds), [rows, n_img, cross_dim]))
+            IGemmArgs a = base_args(u);
+            a.a0 = (const half_t*)image_embeds; a.C0 = embed_dim; a.amode = 0; a.w = u->ip_wproj; a.N = n_img * cross; a.K = embed_dim;
+            a.bias = u->ip_bproj; a.rmode = 0; a.rld = a.N; a.out = u->ip_proj_out; a.omode = 0; a.old = a.N; a.epi = EPI_STORE;
+            a.rows_per_batch = rows; a.M = rows;
+            if (int e = igemm_launch(a, s)) return e;
+            if (int e = cfgpp_op_layernorm(u->ip_proj_out, u->ip_tok, u->ip_ng, u->ip_nb, (long)rows * n_img, cross, 1e-5f, s)) return e;
+        }
+        for (const auto& b : u->ip_blocks) {
+            // slots [96, 128) cleared first: a smaller n_img after a larger one leaves no stale keys
+            if (int e = cfgpp_op_attention_clear_slots(b.ck, b.cvt, u->max_rows * b.nheads, b.d, u->ip_ck_pad, cfgpp_unet::IP_SLOT, cfgpp_unet::IP_MAX, s)) return e;
+            IGemmArgs a = base_args(u);     // the form of the text K / V^T launch of ctx_plan, the image tokens as the batch's rows
+            a.a0 = u->ip_tok; a.C0 = cross; a.amode = 0; a.w = b.wkv; a.N = 2 * b.C; a.K = cross; a.epi = EPI_HEADS;
+            a.hq = nullptr; a.hk = b.ck + (size_t)cfgpp_unet::IP_SLOT * b.dp; a.hvt = b.cvt + cfgpp_unet::IP_SLOT;
+            a.part0 = 1; a.part_width = b.C; a.head_dim = b.d; a.head_dim_pad = b.dp; a.heads = b.nheads;
+            a.tok_pad = u->ip_ck_pad; a.q_tok_pad = u->ip_ck_pad; a.rows_per_batch = n_img; a.M = rows * n_img;
+            if (int e = igemm_launch(a, s)) return e;
+        }
+        u->ip_src = image_embeds; u->ip_rows = rows;
+    }
+    u->ip_set_active(true, n_img, scale);
+    return 0;
+}
+
 int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale) {
     CFGPP_REQUIRE(u && u->finalized, "attach_control: UNet not finalized");
     CFGPP_REQUIRE(!u->control, "attach_control: the target is itself a ControlNet");
@@ -802,6 +1019,8 @@ int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
                   "forward: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",
                   u->cfg.in_channels, z_rows, u->cond_rows);
     CFGPP_REQUIRE(!u->control || u->img_rows > 0, "forward: ControlNet without a control image (call cfgpp_unet_image_condition first)");
+    CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "forward: the image context (IP-Adapter) was set for %d rows, the forward runs %d: call "
+                  "cfgpp_unet_image_context after cfgpp_unet_set_context", u->ip_rows, rows);
     if (u->ctrl && u->ctrl_scale != 0.f) {          // the attached ControlNet's forward first: its residuals feed this plan
         cfgpp_unet* cn = u->ctrl;
         CFGPP_REQUIRE(cn->img_rows > 0, "forward: a ControlNet is attached but has no control image (cfgpp_unet_image_condition)");
@@ -856,11 +1075,14 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
         u->step_tab_cap = cap;
     }
     u->enter_call(rows, z_rows);           // a graph captured in the other mode (switch flipped since) must not hit: the serial moves
-    const cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
+    CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "sample_graph: the image context (IP-Adapter) was set for %d rows, the loop runs %d", u->ip_rows, rows);
+    cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
+    want.ip_active = u->ip_active ? 1 : 0; want.ip_n_img = u->ip_n_img; std::memcpy(&want.ip_scale_bits, &u->ip_scale, sizeof(float));
     auto same = [&](const cfgpp_unet::GraphKey& k) {
         return k.z == want.z && k.z0t == want.z0t && k.eps == want.eps && k.euc == want.euc && k.ec == want.ec && k.z_half == want.z_half &&
                k.z_rows == want.z_rows && k.rows == want.rows && k.tw == want.tw && k.rn == want.rn && k.lam == want.lam && k.n == want.n &&
-               k.tuned_serial == u->tuned_serial && k.cond_rows == want.cond_rows;
+               k.tuned_serial == u->tuned_serial && k.cond_rows == want.cond_rows && k.ip_active == want.ip_active &&
+               k.ip_n_img == want.ip_n_img && k.ip_scale_bits == want.ip_scale_bits;
     };
     int hit = -1;
     for (size_t i = 0; i < u->graphs.size(); ++i) if (same(u->graphs[i].key)) hit = (int)i;
@@ -915,6 +1137,7 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
                        void* stream, double* out_ms, double* out_flops, int* out_launches, char* detail, long detail_cap) {
     CFGPP_REQUIRE(u && u->finalized && u->ctx_set, "profile: context not ready");
     CFGPP_REQUIRE(z && eps_out && out_ms && out_flops && out_launches && rows == u->ctx_rows, "profile: bad args");
+    CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "profile: the image context (IP-Adapter) was set for %d rows", u->ip_rows);
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->out_eps = eps_out;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = u->plan.size();
@@ -981,7 +1204,8 @@ double cfgpp_unet_flops(cfgpp_unet* u, int rows) {
     if (!u || !u->finalized) return 0.0;
     // the prefix a CFG call shares is computed once for both halves: counted once when the most recent forward shared it
     const double once = u->ran_shared == 1 ? u->prefix_macs_per_row * (rows / 2) : 0.0;
-    return 2.0 * ((u->macs_per_row + u->attn_macs_per_row) * rows - once);
+    const double ip = u->ip_active ? u->ip_macs_per_key * u->ip_n_img : 0.0;      // the image keys, while an adapter is active
+    return 2.0 * ((u->macs_per_row + u->attn_macs_per_row + ip) * rows - once);
 }
 
 void cfgpp_unet_set_share_prefix(int on) { g_share_prefix = on ? 1 : 0; }

@@ -317,6 +317,43 @@ class HipUNet:
         check(self.lib.cfgpp_unet_read_weight(self._h, key.encode(), out.data_ptr()), f"cfgpp_unet_read_weight({key})")
         return out
 
+    # -- IP-Adapter --------------------------------------------------------------------
+    def ip_load(self, key: Optional[str], t: Optional[torch.Tensor] = None):
+        """one adapter tensor by its engine key (include/cfgpp_ip_adapter.h: cfgpp_unet_ip_load); ``key is None`` drops the adapter"""
+        if key is None:
+            check(self.lib.cfgpp_unet_ip_load(self._h, None, None, 0, None, 0), "cfgpp_unet_ip_load(NULL)")
+            self._keep.pop("ip_embeds", None)
+            return
+        t = t.detach().cpu().contiguous()
+        if t.dtype == torch.float16:
+            dt = 1
+        else:
+            t = t.to(torch.float32)
+            dt = 0
+        shape = (C.c_long * t.dim())(*t.shape)
+        check(self.lib.cfgpp_unet_ip_load(self._h, key.encode(), t.data_ptr(), dt, shape, t.dim()), f"cfgpp_unet_ip_load({key})")
+
+    def set_image_context(self, image_embeds: Optional[torch.Tensor], scale: float = 1.0):
+        """image_embeds [rows, embed_dim] (uc rows first, then c rows; rows of the current text context); None or scale 0
+        deactivates (include/cfgpp_ip_adapter.h: cfgpp_unet_image_context).  The engine identifies the embeds by address, so the tensor
+        of the last call is kept alive here and an equal tensor is not copied again."""
+        dev = torch.device("cuda", self.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if image_embeds is None or float(scale) == 0.0:
+            check(self.lib.cfgpp_unet_image_context(self._h, None, 0, 0, 0.0, stream), "cfgpp_unet_image_context")
+            return
+        e = image_embeds.to(device=dev, dtype=torch.float16).contiguous()
+        if e.dim() != 2:
+            raise CfgppError(f"set_image_context: image_embeds shape {tuple(e.shape)}, expected [rows, embed_dim]")
+        old = self._keep.get("ip_embeds")
+        if old is not None and old.shape == e.shape and bool(torch.equal(old, e)):
+            e = old                         # the same values: only the scale changes, nothing is projected again
+        else:
+            e = e.clone()                   # a private copy (the old one is still alive: a new address), safe from in-place edits
+        check(self.lib.cfgpp_unet_image_context(self._h, e.data_ptr(), int(e.shape[0]), int(e.shape[1]), float(scale), stream),
+              "cfgpp_unet_image_context")
+        self._keep["ip_embeds"] = e
+
     def attach_control(self, cn, scale: float):
         """attach ControlNet ``cn`` (a finalized :class:`cfgpp_amd.controlnet.HipControlNet`; None detaches) with
         ``conditioning_scale`` (include/cfgpp.h: cfgpp_unet_attach_control).  Synchronises the device."""

@@ -62,6 +62,7 @@ class HipEngine:
         from .lora import LoraState
         self._lora = LoraState(cfg, self.unet.lora)
         self._control = None         # (HipControlNet, scale) while a control is set
+        self._ip = None              # the parsed IP-Adapter while one is loaded
         self._eps = None
         self._g_buf = None
         # opt-in guard for the first runs with a real checkpoint (real SDXL activations approach the fp16 maximum in the deep
@@ -126,6 +127,38 @@ class HipEngine:
     @property
     def control(self):
         return self._control
+
+    # -- IP-Adapter -------------------------------------------------------------------
+    def set_ip_adapter(self, spec):
+        """load an IP-Adapter (``ip_adapter.resolve``: "synthetic", a safetensors path, a state dict, a parsed adapter) into the
+        UNet, or drop it (None).  UNet weights, tile pins and captured graphs are untouched (include/cfgpp_ip_adapter.h: cfgpp_unet_ip_load)."""
+        from .ip_adapter import resolve
+        parsed = resolve(spec, self.cfg)
+        if self._ip is not None:     # the drop synchronises the device and clears every block's image slots: only when there is one
+            self.unet.ip_load(None)
+        self._ip = None
+        if parsed is not None:
+            for k, v in parsed.items():
+                self.unet.ip_load(k, v)
+            self._ip = parsed
+        return self
+
+    @property
+    def ip_adapter(self):
+        return self._ip
+
+    def set_image_embeds(self, embeds: Optional[torch.Tensor], negative: Optional[torch.Tensor] = None, scale: float = 1.0):
+        """image prompt of the next predictions: ``embeds`` [1 or B, embed_dim] (None deactivates), ``negative`` None = zeros; call
+        after ``set_context`` (the rows are the text context's)."""
+        if embeds is None or float(scale) == 0.0:
+            self.unet.set_image_context(None)
+            return
+        if self.ip_adapter is None:
+            raise CfgppError("ip_adapter_image_embeds given but no IP-Adapter is loaded (get_solver(..., ip_adapter=...) / set_ip_adapter)")
+        from .ip_adapter import assemble_embeds
+        if int(embeds.shape[-1]) != self.ip_adapter.embed_dim:
+            raise CfgppError(f"ip_adapter_image_embeds: embed_dim {int(embeds.shape[-1])}, the adapter takes {self.ip_adapter.embed_dim}")
+        self.unet.set_image_context(assemble_embeds(embeds, negative, self.B), float(scale))
 
     # -- LoRA ------------------------------------------------------------------------
     def set_lora(self, adapters, ignore_text_encoder: bool = False):

@@ -46,19 +46,32 @@ def controlled(sample):
     """``sample(..., control_image=None, controlnet_conditioning_scale=1.0)``: with a control image, the solver's ControlNet
     (``get_solver(..., controlnet=...)``) is attached to the engine for this call - every UNet prediction of the loop, whatever
     the solver, follows it (diffusers StableDiffusion(XL)ControlNetPipeline, one net, non-guess mode); without one the engine
-    runs the plain UNet.  Solvers whose ``controllable`` is False (inversion, edit, inpaint) refuse a control image."""
+    runs the plain UNet.  Solvers whose ``controllable`` is False (inversion, edit, inpaint) refuse a control image.
+
+    ``sample(..., ip_adapter_image_embeds=[1 or B, embed_dim] | ip_adapter_image=[1 or B, 3, H, W] in [0, 1],
+    negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0)``: an image prompt for the solver's IP-Adapter
+    (``get_solver(..., ip_adapter=...)`` / ``set_ip_adapter``) for this call; the same solvers refuse these arguments."""
     @functools.wraps(sample)
     def run(self, *args, **kwargs):
         image = kwargs.pop("control_image", None)
         scale = kwargs.pop("controlnet_conditioning_scale", 1.0)
+        ip = {k: kwargs.pop(k, None) for k in ("ip_adapter_image_embeds", "negative_ip_adapter_image_embeds", "ip_adapter_image")}
+        ip_scale = kwargs.pop("ip_adapter_scale", 1.0)
+        if any(v is not None for v in ip.values()) and not self.controllable:
+            raise ValueError(f"{type(self).__name__}.sample() does not take ip_adapter_image_embeds / ip_adapter_image: IP-Adapter image "
+                             "prompts are for the text-to-image solvers (inversion, edit and inpaint solvers refuse them)")
+        self._ip_job = self._ip_prepare(ip, ip_scale)
         lora_scale = kwargs.pop("lora_scale", None)
         if lora_scale is not None:          # shorthand: every adapter of the solver at this scale, from this job on
             self.set_lora_scale(lora_scale)
         if image is not None and not self.controllable:
             raise ValueError(f"{type(self).__name__}.sample() does not take control_image: ControlNet conditioning is for the "
                              "text-to-image solvers (inversion, edit and inpaint solvers refuse it)")
-        with self._control(image, scale):
-            return sample(self, *args, **kwargs)
+        try:
+            with self._control(image, scale):
+                return sample(self, *args, **kwargs)
+        finally:
+            self._ip_job = None
     return run
 
 
@@ -118,6 +131,16 @@ class StableDiffusion:
                 raise ValueError(f"controlnet=...: the engine {type(engine).__name__} cannot build a ControlNet")
             self.controlnet = engine.build_controlnet(cn, seed=kwargs.get("controlnet_seed", 0))
 
+        # IP-Adapter ("synthetic", a safetensors path, a state dict): loaded into the UNet; used by the sample() calls that pass
+        # ip_adapter_image_embeds / ip_adapter_image.  ip_adapter_dir: the folder that holds the CLIP `image_encoder/`.
+        self._ip_job = None                 # (embeds, negative, scale, serial) of the running sample() call
+        self._ip_key = None                 # what the engine's image context was last set from
+        self._ip_serial = 0
+        self.ip_adapter_dir = kwargs.get("ip_adapter_dir")
+        self.image_encoder = kwargs.get("image_encoder")
+        if kwargs.get("ip_adapter") is not None:
+            self.set_ip_adapter(kwargs["ip_adapter"])
+
         if kwargs.get("lora"):              # [(safetensors path | state dict | parsed, scale), ...] merged into the UNet on the device
             self.set_lora(kwargs["lora"], ignore_text_encoder=kwargs.get("lora_ignore_text_encoder", False))
 
@@ -161,6 +184,60 @@ class StableDiffusion:
         cur = eng.lora_adapters
         if any(float(s) != float(scale) for _, s in cur):
             eng.set_lora([(p, float(scale)) for p, _ in cur])
+
+    # ------------------------------------------------------------------ IP-Adapter
+    def set_ip_adapter(self, spec):
+        """load an IP-Adapter into the engine's UNet (``ip_adapter.resolve``: "synthetic" | safetensors path | state dict), or drop
+        it (None)"""
+        if not hasattr(self.engine, "set_ip_adapter"):
+            raise ValueError(f"ip_adapter=...: the engine {type(self.engine).__name__} cannot load an IP-Adapter")
+        self.engine.set_ip_adapter(spec)
+        self._ip_key = object()         # whatever image context the engine had is gone
+
+    def _ip_prepare(self, ip, scale):
+        """the image prompt of one sample() call -> (embeds, negative embeds | None, scale) or None"""
+        emb, neg, img = ip["ip_adapter_image_embeds"], ip["negative_ip_adapter_image_embeds"], ip["ip_adapter_image"]
+        if emb is None and img is None:
+            if neg is not None:
+                raise ValueError("negative_ip_adapter_image_embeds without ip_adapter_image_embeds / ip_adapter_image")
+            return None
+        if emb is not None and img is not None:
+            raise ValueError("pass ip_adapter_image_embeds or ip_adapter_image, not both")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("IP-Adapter image prompts are not supported in sharded runs (world size > 1): the per-chain embeds are not sharded")
+        if not hasattr(self.engine, "set_image_embeds") or getattr(self.engine, "ip_adapter", None) is None:
+            raise ValueError("ip_adapter_image_embeds / ip_adapter_image given, but the solver has no IP-Adapter: "
+                             "get_solver(..., ip_adapter=\"synthetic\" | path | state_dict)")
+        if img is not None:                 # CLIP image tower: torch ops, once per job (ip_adapter.ImageEncoder)
+            if self.image_encoder is None:
+                if not self.ip_adapter_dir:
+                    raise ValueError("ip_adapter_image needs the CLIP image encoder: get_solver(..., ip_adapter_dir=<folder holding image_encoder/>)")
+                from .ip_adapter import ImageEncoder
+                self.image_encoder = ImageEncoder(self.ip_adapter_dir, self.work_device)
+            emb = self.image_encoder(img)
+        self._ip_serial += 1
+        return (emb, neg, float(scale), self._ip_serial)
+
+    def _ensure_image_context(self, ctx_changed: bool, uc, c):
+        """after the text context: (re)project the call's image prompt, or switch the adapter off (once per sampling loop)"""
+        job, eng = self._ip_job, self.engine
+        if not hasattr(eng, "set_image_embeds"):
+            return
+        key = None if job is None else (job[3], uc is None, c is None)
+        if not ctx_changed and self._ip_key == key:
+            return
+        if job is None:
+            eng.set_image_embeds(None)
+        else:
+            emb, neg, scale = job[:3]
+            if uc is None:                  # single forward on the conditional rows: both halves carry the image prompt
+                neg = emb
+            elif c is None:
+                emb = torch.zeros_like(emb) if neg is None else neg
+                neg = emb
+            eng.set_image_embeds(emb, neg, scale)
+        self._ip_key = key
 
     def _lora_epoch(self) -> int:
         return int(getattr(self.engine, "lora_epoch", 0))
@@ -227,10 +304,12 @@ class StableDiffusion:
         a = c if uc is None else uc
         b = uc if c is None else c
         key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch())
-        if getattr(self, "_ctx_key", None) != key:
+        changed = getattr(self, "_ctx_key", None) != key
+        if changed:
             self._set_context(a, b)
             self._ctx_key = key
             self._ctx_keep = (a, b)
+        self._ensure_image_context(changed, uc, c)
 
     # ------------------------------------------------------------------ whole-loop graph replay
     def _graph_loop(self, zt, ts, uc, c, lam, tweedie_uc, renoise_uc, coeff_of):

@@ -107,7 +107,8 @@ class SDXL(StableDiffusion):
         te, ti = added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]
         key = (a.data_ptr(), b.data_ptr(), te.data_ptr(), ti.data_ptr(), tuple(te.shape), tuple(a.shape), tuple(b.shape),
                a._version, b._version, te._version, ti._version, self._lora_epoch())
-        if getattr(self, "_ctx_key", None) != key:
+        changed = getattr(self, "_ctx_key", None) != key
+        if changed:
             B = max(int(a.shape[0]), int(b.shape[0]))
             rows = 2 * B
             # cond rows: 2B ([neg.., pos..]) or B / 1 (positive only -> applied to both halves, quirk Q7)
@@ -118,6 +119,7 @@ class SDXL(StableDiffusion):
             self.engine.set_context(a, b, te_full, ti_full)
             self._ctx_key = key
             self._ctx_keep = (a, b, te, ti)
+        self._ensure_image_context(changed, uc, c)
 
     # ------------------------------------------------------------------ sample
     def _sizes(self, original_size, target_size):

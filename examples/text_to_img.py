@@ -2,7 +2,8 @@
 
     python examples/text_to_img.py --prompt "a corgi" --method ddim_cfg++ --cfg_guidance 0.6 --NFE 50 \
         [--model sd15|sdxl|sdxl_lightning] [--unet_weights unet.safetensors --vae_weights vae.safetensors] \
-        [--batch 8] [--draw] [--controlnet_dir <diffusers controlnet/ folder> --control_image edges.png]
+        [--batch 8] [--draw] [--controlnet_dir <diffusers controlnet/ folder> --control_image edges.png] \
+        [--ip_adapter ip-adapter_sd15.safetensors[:SCALE] (--ip_image ref.png --ip_adapter_dir <folder with image_encoder/> | --ip_embeds e.npy)]
 
 Differences from the reference, all additive: ``--unet_weights / --vae_weights`` (diffusers-layout safetensors;
 default = seeded synthetic weights, because no checkpoint exists offline), ``--batch`` (B chains with seeds
@@ -52,6 +53,11 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--model", default="sd15", choices=("sd15", "sd20", "sdxl", "sdxl_lightning"))
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
+    ap.add_argument("--ip_adapter", default=None, metavar="PATH[:SCALE]",
+                    help="IP-Adapter safetensors file (ip-adapter_sd15 / _sdxl / _sdxl_vit-h, or 'synthetic'); needs --ip_image or --ip_embeds")
+    ap.add_argument("--ip_image", default=None, help="reference picture (PNG / JPEG) for the IP-Adapter; needs --ip_adapter_dir")
+    ap.add_argument("--ip_adapter_dir", default=None, help="folder that holds the CLIP image tower (image_encoder/)")
+    ap.add_argument("--ip_embeds", default=None, metavar="FILE.npy", help="precomputed CLIP image embeds [1 or batch, embed_dim]")
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
     args = ap.parse_args(argv)
 
@@ -78,6 +84,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         from cfgpp_amd.lora import parse_cli
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
+    ip_kwargs = _ip_kwargs(args, kw)
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference
@@ -87,17 +94,44 @@ def main(argv=None, solver_kwargs=None) -> None:
         solver = get_solver(args.method, **kw)
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
                                cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver))
+                               **_control_kwargs(args, solver), **ip_kwargs)
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
         solver = get_solver(args.method, **kw)
         result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver))
+                               **_control_kwargs(args, solver), **ip_kwargs)
 
     for i in range(result.shape[0]):
         name = "generated.png" if result.shape[0] == 1 else f"generated_{i}.png"
         save_image(result[i:i + 1], args.workdir / "result" / name, normalize=True)
     print(f"saved {result.shape[0]} image(s) to {args.workdir / 'result'}")
+
+
+def _ip_kwargs(args, kw):
+    """--ip_adapter PATH[:SCALE] with --ip_image / --ip_embeds -> solver kwargs added to ``kw``, sample() kwargs returned"""
+    if not args.ip_adapter:
+        if args.ip_image or args.ip_embeds:
+            raise SystemExit("--ip_image / --ip_embeds need --ip_adapter (an IP-Adapter safetensors file, or 'synthetic')")
+        return {}
+    path, _, scale = args.ip_adapter.rpartition(":")
+    try:
+        scale = float(scale) if path else 1.0
+    except ValueError:
+        path, scale = args.ip_adapter, 1.0
+    kw["ip_adapter"] = path or args.ip_adapter
+    if bool(args.ip_image) == bool(args.ip_embeds):
+        raise SystemExit("--ip_adapter needs exactly one of --ip_image (with --ip_adapter_dir) and --ip_embeds")
+    if args.ip_embeds:
+        import numpy as np
+        emb = torch.from_numpy(np.load(args.ip_embeds)).float()
+        return dict(ip_adapter_image_embeds=emb.reshape(-1, emb.shape[-1]), ip_adapter_scale=scale)
+    if not args.ip_adapter_dir:
+        raise SystemExit("--ip_image needs --ip_adapter_dir (the folder that holds the CLIP image_encoder/)")
+    kw["ip_adapter_dir"] = args.ip_adapter_dir
+    from PIL import Image
+    import numpy as np
+    img = torch.from_numpy(np.asarray(Image.open(args.ip_image).convert("RGB"), dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous()
+    return dict(ip_adapter_image=img, ip_adapter_scale=scale)
 
 
 def _control_kwargs(args, solver):

@@ -229,6 +229,9 @@ int cfgpp_unet_attach_control(cfgpp_unet* u, cfgpp_unet* cn, float scale);
  * valid until the launch ran (stream-ordered allocations freed after the call are fine). */
 int cfgpp_unet_lora(cfgpp_unet* u, const char* key, const float* up, const float* down, int rank, void* stream);
 
+/* ---- IP-Adapter image prompts: two further entry points on a finalized UNet engine - load the adapter, set the image context -
+ * are declared in include/cfgpp_ip_adapter.h, an extension header of this boundary, exported by the same library. */
+
 /* Algorithmic FLOPs (2*MAC over conv/linear/attention matmuls) of one forward at `rows`.  When the most recent forward shared
  * the CFG prefix (rows == 2 * z_rows on a net without add_embedding: the ops before the first cross-attention ran once for
  * both halves), those ops count once - the figure is the work that was done. */
