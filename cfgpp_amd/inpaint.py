@@ -15,14 +15,13 @@ have their own: ``get_inpaint_solver(name, model="sd15" | "sdxl", **get_solver k
 """
 from __future__ import annotations
 
-from contextlib import contextmanager
 from typing import Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 
 from . import coeffs as K
-from .latent_diffusion import StableDiffusion, _progress, controlled
+from .latent_diffusion import StableDiffusion, controlled
 from .latent_sdxl import SDXL
 from .registry import Registry
 
@@ -74,7 +73,7 @@ def strength_timesteps(timesteps: torch.Tensor, strength: float):
 
 
 class _InpaintMixin:
-    """shared by the SD1.5 and SDXL classes: mask / source preparation, the start latent, the masked eager loop"""
+    """shared by the SD1.5 and SDXL classes: mask / source preparation, the start latent, the masked update"""
 
     cfgpp = False
     controllable = False        # ControlNet on inpaint UNets is not supported: sample() refuses control_image
@@ -83,15 +82,6 @@ class _InpaintMixin:
     def inpaint_unet(self) -> bool:
         """a 9-channel UNet (mask + masked-image latent as input channels) rather than the masked update"""
         return self.cfg.in_channels > self.cfg.out_channels
-
-    @contextmanager
-    def _loop_timesteps(self, ts):
-        full = self.scheduler.timesteps
-        self.scheduler.timesteps = ts
-        try:
-            yield
-        finally:
-            self.scheduler.timesteps = full
 
     def _graph_loop(self, *args, **kwargs):
         if getattr(self, "_blend", None) is not None:       # the masked update has no graph form: eager loop
@@ -133,24 +123,18 @@ class _InpaintMixin:
             zt = noise
         return zt, ts
 
-    def _masked_loop(self, zt, ts, predict, lam, wrap: bool, callback_fn=None, desc="inpaint"):
-        """the DDIM loop of ``_ddim_forward`` with the fused masked update; returns (z0t, zt)"""
+    def _masked_update(self, zt, z0t, noise_uc, noise_c, lam, sqrt4, tweedie_uc, renoise_uc, device_alpha=None, last=False):
+        """``_ddim_update`` with the fused masked update (4-channel UNet; fp32 latent, fp16 eps)"""
         mask, z_src, noise = self._blend
-        zt = self._own_latent(zt)
-        z0t = torch.empty_like(zt)
-        ts = ts.int() if wrap else ts
-        n = len(ts)
-        for step, t in enumerate(_progress(ts, desc)):
-            sqrt4 = self.tables.ddim_sqrt_coeffs(t, wrap=wrap)
-            noise_uc, noise_c = predict(zt, t)
-            dev_a = "rn" if (not wrap and int(t) - self.tables.skip < 0) else None
-            co = K.ddim_coeffs_pinned(sqrt4, eps_half=True, semantics=self.scalar_semantics, z_half=False, device_alpha=dev_a)
-            # the source forward-noised to this step's target timestep; the clean source after the last step
-            a, b = (sqrt4[2], sqrt4[3]) if step < n - 1 else (1.0, 0.0)
-            self.engine.step_ddim_masked(zt, z0t, noise_uc, noise_c, lam, co, False, self.cfgpp, mask, z_src, noise, a, b)
-            if callback_fn is not None:
-                self._run_callback(callback_fn, step, t, z0t, zt)
-        return z0t, zt
+        co = K.ddim_coeffs_pinned(sqrt4, eps_half=True, semantics=self.scalar_semantics, z_half=False, device_alpha=device_alpha)
+        # the source forward-noised to this step's target timestep; the clean source after the last step
+        a, b = (1.0, 0.0) if last else (sqrt4[2], sqrt4[3])
+        self.engine.step_ddim_masked(zt, z0t, noise_uc, noise_c, lam, co, tweedie_uc, renoise_uc, mask, z_src, noise, a, b)
+
+    def _inpaint_loop(self, zt, ts, uc, c, lam, wrap: bool, added=None, callback_fn=None, desc="inpaint"):
+        """the DDIM loop over ``ts``: the plain update for a 9-channel UNet, the masked one otherwise; returns (z0t, zt)"""
+        return self._ddim_loop(zt, uc, c, lam, False, self.cfgpp, wrap=wrap, added=added, ts=ts, callback_fn=callback_fn, desc=desc,
+                               update=None if self._blend is None else self._masked_update)
 
 
 # ---------------------------------------------------------------------------------------------------- SD1.5
@@ -168,16 +152,8 @@ class InpaintDDIM(_InpaintMixin, StableDiffusion):
         uc, c = self._embeds(prompt, kwargs)
         B = int(c.shape[0])
         zt, ts = self._prepare_job(src_img, mask, strength, B, kwargs.get("seeds"), wrap=False)
-        if self._blend is None:
-            with self._loop_timesteps(ts):
-                z0t, zt = self._ddim_forward(zt, uc, c, cfg_guidance, self.cfgpp, callback_fn, desc="SD-inpaint")
-        else:
-            self._ensure_context(uc, c)
-            z0t, zt = self._masked_loop(zt, ts, lambda z, t: self.predict_noise(z, t, uc, c), cfg_guidance, False, callback_fn,
-                                        "SD-inpaint")
-        if kwargs.get("return_latents"):
-            return z0t, zt
-        return self._finish(z0t)
+        z0t, zt = self._inpaint_loop(zt, ts, uc, c, cfg_guidance, False, callback_fn=callback_fn, desc="SD-inpaint")
+        return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
 class InpaintDDIMCFGpp(InpaintDDIM):
@@ -212,14 +188,8 @@ class InpaintDDIMXL(_InpaintMixin, SDXL):
                         callback_fn=None, src_img=None, mask=None, strength: float = 1.0, seeds=None, **kwargs):
         B = int(prompt_embeds.shape[0])
         zt, ts = self._prepare_job(src_img, mask, strength, B, seeds, wrap=True)
-        if self._blend is None:
-            with self._loop_timesteps(ts):
-                return self._ddim_xl(null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape, self.cfgpp,
-                                     callback_fn, wrap=True, zt=zt, desc="SDXL-inpaint")
-        self._ensure_context(null_prompt_embeds, prompt_embeds, add_cond_kwargs)
-        z0t, _ = self._masked_loop(zt, ts, lambda z, t: self.predict_noise(z, t, null_prompt_embeds, prompt_embeds, add_cond_kwargs),
-                                   cfg_guidance, True, callback_fn, "SDXL-inpaint")
-        return z0t
+        return self._inpaint_loop(zt, ts, null_prompt_embeds, prompt_embeds, cfg_guidance, True, add_cond_kwargs, callback_fn,
+                                  "SDXL-inpaint")[0]
 
 
 class InpaintDDIMXLCFGpp(InpaintDDIMXL):

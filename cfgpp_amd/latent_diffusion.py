@@ -289,7 +289,11 @@ class StableDiffusion:
     def predict_noise(self, zt: torch.Tensor, t, uc: Optional[torch.Tensor], c: Optional[torch.Tensor]):
         """epsilon_theta for null and condition (latent_diffusion.py:131-158).  One
         UNet launch over rows [uc_1..uc_B, c_1..c_B]; ``zt`` is read twice by index."""
-        self._ensure_context(uc, c)
+        return self._predict(zt, t, uc, c)
+
+    def _predict(self, zt, t, uc, c, added=None):
+        """``predict_noise`` of both families; ``added``: SDXL's ``added_cond_kwargs``"""
+        self._ensure_context(uc, c, added)
         noise_uc, noise_c = self.engine.predict(zt, float(t))
         if uc is None:
             return noise_c, noise_c
@@ -297,32 +301,47 @@ class StableDiffusion:
             return noise_uc, noise_uc
         return noise_uc, noise_c
 
-    def _ensure_context(self, uc, c):
+    def _ensure_context(self, uc, c, added=None):
         """(re)build the engine's conditioning when the embeddings changed (once per sampling loop)"""
         if uc is None and c is None:
             raise ValueError("predict_noise needs at least one of uc / c")
         a = c if uc is None else uc
         b = uc if c is None else c
-        key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch())
+        extra, extra_key = self._added_context(added)
+        key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch(), *extra_key)
         changed = getattr(self, "_ctx_key", None) != key
         if changed:
-            self._set_context(a, b)
+            self._set_context(a, b, *extra)
             self._ctx_key = key
-            self._ctx_keep = (a, b)
+            self._ctx_keep = (a, b, *extra)
         self._ensure_image_context(changed, uc, c)
 
-    # ------------------------------------------------------------------ whole-loop graph replay
-    def _graph_loop(self, zt, ts, uc, c, lam, tweedie_uc, renoise_uc, coeff_of):
-        """The DDIM loops with callback_fn None as hipGraph replays of ONE captured step (UNet + fused update; include/cfgpp.h:
+    def _added_context(self, added):
+        """-> (tensors that travel with the text context, what they add to the cache key): none for SD1.5"""
+        return (), ()
+
+    # ------------------------------------------------------------------ the DDIM step rule; whole-loop graph replay
+    def _ddim_step_coeffs(self, t, inversion: bool, wrap: bool):
+        """The DDIM step at timestep ``t`` -> (sqrt4, device_alpha), for the eager loop and the graph's step table alike.
+        sqrt4: the pinned sqrt(at) etc. of at = alpha(t), at_prev = alpha(t - skip), swapped for an inversion.  device_alpha:
+        which of the two is a DEVICE scalar (coeffs.py) - alpha(t - skip) of the step that leaves the table is
+        ``final_alpha_cumprod.to(device)``: the renoising alpha ("rn") forward, the x0-estimate alpha ("tw") in an inversion.
+        ``wrap`` (quirk Q3): SDXL's `ddim` loops index the shifted table unguarded and never take the final alpha."""
+        sqrt4 = self.tables.ddim_sqrt_coeffs(t, wrap=wrap, inversion=inversion)
+        final = not wrap and int(t) - self.tables.skip < 0
+        return sqrt4, (("tw" if inversion else "rn") if final else None)
+
+    def _graph_loop(self, zt, ts, uc, c, lam, tweedie_uc, renoise_uc, inversion, wrap):
+        """The DDIM loop with callback_fn None as hipGraph replays of ONE captured step (UNet + fused update; include/cfgpp.h:
         cfgpp_sample_graph_ddim) when the engine offers it ($CFGPP_GRAPH=1 on the HIP engine): the per-step scalars - exactly
-        what the eager loop hands to ``predict`` / ``step_ddim`` - are computed up front.  ``coeff_of(t) -> (sqrt4, device_alpha)``.
+        what the eager loop hands to ``predict`` / ``step_ddim`` - are computed up front.
         Returns (z0t, zt) or None when the eager loop has to run (mock engine, switch off)."""
         if not getattr(self.engine, "graph_enabled", False):
             return None
         z_half = zt.dtype == torch.float16
         steps = []
         for t in ts:
-            sqrt4, dev_a = coeff_of(t)
+            sqrt4, dev_a = self._ddim_step_coeffs(t, inversion, wrap)
             co = K.ddim_coeffs_pinned(sqrt4, eps_half=True, semantics=self.scalar_semantics, z_half=z_half, device_alpha=dev_a)
             steps.append((float(t), *[float(v) for v in co]))
         single = "c" if uc is None else ("uc" if c is None else "")
@@ -379,7 +398,7 @@ class StableDiffusion:
         return x - model_pred * sigma
 
     # ------------------------------------------------------------------ fused loops
-    def _ddim_update(self, zt, z0t, noise_uc, noise_c, lam, sqrt4, tweedie_uc, renoise_uc, device_alpha=None):
+    def _ddim_update(self, zt, z0t, noise_uc, noise_c, lam, sqrt4, tweedie_uc, renoise_uc, device_alpha=None, last=False):
         co = K.ddim_coeffs_pinned(sqrt4, eps_half=(noise_uc.dtype == torch.float16), semantics=self.scalar_semantics,
                                   z_half=(zt.dtype == torch.float16), device_alpha=device_alpha)
         self.engine.step_ddim(zt, z0t, noise_uc, noise_c, lam, co, tweedie_uc, renoise_uc)
@@ -397,51 +416,44 @@ class StableDiffusion:
         if kw["zt"] is not zt:
             zt.copy_(kw["zt"])
 
-    def _ddim_forward(self, zt, uc, c, cfg_guidance, cfgpp: bool, callback_fn=None, desc="SD", wrap_index=False):
-        """DDIM / DDIM-CFG++ reverse loop (latent_diffusion.py:272-294 / 652-674).
-        ``zt`` [B,4,H,W] on the engine device: fp32 (text-to-image: ``torch.randn``) or fp16 (after an
-        inversion that started from the fp16 VAE latent); a private copy is updated in place; returns (z0t, zt)."""
+    def _ddim_loop(self, zt, uc, c, lam, tweedie_uc: bool, renoise_uc: bool, *, inversion=False, wrap=False, added=None, ts=None,
+                   callback_fn=None, desc="SD", update=None):
+        """THE DDIM loop of both families: reverse DDIM / DDIM-CFG++ (latent_diffusion.py:272-294 / 652-674, latent_sdxl.py:
+        425-467 / 679-703) and, with ``inversion``, DDIM inversion over the reversed timesteps (latent_diffusion.py:160-182 CFG,
+        888-910 CFG++; latent_sdxl.py:301-320).  ``tweedie_uc`` / ``renoise_uc``: eps_uc rather than eps_hat in the x0
+        estimate / the renoising.  ``zt`` [B,4,H,W]: fp32 (text-to-image: ``torch.randn``) or fp16 (an inversion that starts
+        from the fp16 VAE latent, and the regeneration after it); a private copy is updated in place.  ``added``: SDXL's
+        ``added_cond_kwargs``; ``ts``: other timesteps than the scheduler's; ``update``: another fused update than
+        ``_ddim_update``, same arguments (``last``: the loop's last step).  Returns (z0t, zt)."""
         zt = self._own_latent(zt)
-        ts = self.scheduler.timesteps
-        ts = ts.int() if wrap_index else ts
+        if ts is None:
+            ts = self.scheduler.timesteps.flip(0) if inversion else self.scheduler.timesteps
+        ts = ts.int() if wrap else ts
+        self._ensure_context(uc, c, added)
         if callback_fn is None:
-            self._ensure_context(uc, c)
-            done = self._graph_loop(zt, ts, uc, c, cfg_guidance, False, cfgpp, lambda t: (
-                self.tables.ddim_sqrt_coeffs(t, wrap=wrap_index), "rn" if (not wrap_index and int(t) - self.tables.skip < 0) else None))
+            done = self._graph_loop(zt, ts, uc, c, lam, tweedie_uc, renoise_uc, inversion, wrap)
             if done is not None:
                 return done
+        update = update or self._ddim_update
         z0t = torch.empty_like(zt)
+        n = len(ts)
         for step, t in enumerate(_progress(ts, desc)):
-            # at = alpha(t), at_prev = alpha(t - skip); SDXL loops index the shifted table
-            # unguarded (quirk Q3, wrap_index).  sqrt(at) etc. come from the pinned tables.
-            sqrt4 = self.tables.ddim_sqrt_coeffs(t, wrap=wrap_index)
-            noise_uc, noise_c = self.predict_noise(zt, t, uc, c)
-            # alpha(t - skip) of the last step is `final_alpha_cumprod.to(device)`: a DEVICE scalar (coeffs.py)
-            dev_a = "rn" if (not wrap_index and int(t) - self.tables.skip < 0) else None
-            self._ddim_update(zt, z0t, noise_uc, noise_c, cfg_guidance, sqrt4, False, cfgpp, dev_a)
+            sqrt4, dev_a = self._ddim_step_coeffs(t, inversion, wrap)
+            noise_uc, noise_c = self._predict(zt, t, uc, c, added)
+            update(zt, z0t, noise_uc, noise_c, lam, sqrt4, tweedie_uc, renoise_uc, dev_a, last=(step == n - 1))
             if callback_fn is not None:
                 self._run_callback(callback_fn, step, t, z0t, zt)
         return z0t, zt
 
-    def _ddim_inversion(self, z0, uc, c, cfg_guidance, cfgpp: bool):
-        """DDIM inversion (latent_diffusion.py:160-182 CFG, 888-910 CFG++)."""
-        zt = self._own_latent(z0)
-        self._ensure_context(uc, c)
-        done = self._graph_loop(zt, list(reversed(self.scheduler.timesteps)), uc, c, cfg_guidance, cfgpp, False, lambda t: (
-            self.tables.ddim_sqrt_coeffs(t, inversion=True), "tw" if int(t) - self.tables.skip < 0 else None))
-        if done is not None:
-            return done[1]
-        z0t = torch.empty_like(zt)
-        for t in _progress(reversed(self.scheduler.timesteps), "DDIM Inversion"):
-            sqrt4 = self.tables.ddim_sqrt_coeffs(t, inversion=True)     # a_tw = alpha(t-skip), a_rn = alpha(t)
-            noise_uc, noise_c = self.predict_noise(zt, t, uc, c)
-            dev_a = "tw" if int(t) - self.tables.skip < 0 else None
-            self._ddim_update(zt, z0t, noise_uc, noise_c, cfg_guidance, sqrt4, cfgpp, False, dev_a)
-        return zt
+    inversion_cfgpp = False     # CFG++ inversion: x0 from eps_uc (the renoising keeps eps_hat)
 
     @torch.no_grad()
     def inversion(self, z0, uc, c, cfg_guidance: float = 1.0):
-        return self._ddim_inversion(z0, uc, c, cfg_guidance, cfgpp=False)
+        return self._ddim_loop(z0, uc, c, cfg_guidance, self.inversion_cfgpp, False, inversion=True, desc="DDIM Inversion")[1]
+
+    def _result(self, return_latents, latents, z):
+        """what ``sample`` returns: ``latents`` when asked for them, else the decoded image of ``z``"""
+        return latents if return_latents else self._finish(z)
 
     def _finish(self, z):
         if os.environ.get("CFGPP_TRACE"):
@@ -470,31 +482,35 @@ class StableDiffusion:
         return int(c.shape[0])
 
     # ------------------------------------------------------------------ k-diffusion loop
-    def _kdiff_loop(self, uc, c, cfg_guidance, variant: int, solver: str, callback_fn=None, seeds=None):
-        """Euler / DPM++2M (CFG: variant 0, CFG++: variant 1) on Karras sigmas, fp16 latent
-        (latent_diffusion.py:302-346, 454-503, 682-723, 830-879)."""
-        B = self._batch_of(c, None)
-        sigmas = self.tables.karras_sigmas()
-        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.out_channels) + self.latent_hw,
-                                   sigmas=sigmas, seeds=seeds).to(torch.float16).contiguous()
-        xc = torch.empty_like(x)
-        den = torch.empty_like(x)
-        old = torch.empty_like(x)
+    def _kdiff_start(self, size, sigmas, seeds):
+        """randn * sqrt(sigma0^2 + 1) in fp32, then cast: the fp16 start latent of the Karras-sigma loops (latent_sdxl.py:290-294)"""
+        return self.initialize_latent(method="random_kdiffusion", latent_dim=size, sigmas=sigmas, seeds=seeds).to(torch.float16).contiguous()
+
+    def _kdiff_loop(self, x, sigmas, uc, c, cfg_guidance, variant: int, solver: str, callback_fn=None, *, added=None, n_steps=None,
+                    alphas=None, xl_form=False, t_of_sigma=None, desc="SD"):
+        """THE Euler / DPM++2M loop of both families (CFG: variant 0, CFG++: variant 1, SDXL's 2M CFG++: variant 2 with
+        ``xl_form``) on ``sigmas`` from the fp16 start latent ``x``, updated in place (latent_diffusion.py:302-346, 454-503,
+        682-723, 830-879; latent_sdxl.py:469-517, 757-808, 860-930).  The UNet input is ``x / sqrt(sigma^2 + 1)``, or with
+        ``alphas`` ``x * sqrt(alphas[i])``; ``t_of_sigma``: ``self.timestep`` unless given; ``added``: SDXL's
+        ``added_cond_kwargs``.  Returns (denoised, x)."""
+        xc, den, old = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        t_of_sigma = t_of_sigma or self.timestep
         have_old = False
-        n = len(self.scheduler.timesteps)
-        for i in _progress(range(n), "SD"):
+        for i in _progress(range(len(self.scheduler.timesteps) if n_steps is None else n_steps), desc):
             sigma = sigmas[i]
-            new_t = self.timestep(sigma)
-            self.engine.kdiff_input(x, xc, K.kdiff_input_scale_sd(sigma, self.scalar_semantics), 0)
-            noise_uc, noise_c = self.predict_noise(xc, new_t, uc, c)
+            new_t = t_of_sigma(sigma)
+            if alphas is None:
+                self.engine.kdiff_input(x, xc, K.kdiff_input_scale_sd(sigma, self.scalar_semantics), 0)
+            else:
+                self.engine.kdiff_input(x, xc, float(alphas[i].clone().sqrt()), 1)
+            noise_uc, noise_c = self._predict(xc, new_t, uc, c, added)
             first = (solver == "euler") or (not have_old)
-            coef, euler = K.kdiff_coeffs(cfg_guidance, sigmas, i, first, xl_form=False, semantics=self.scalar_semantics)
-            self.engine.step_kdiff(x, den, old, noise_uc, noise_c, coef, variant, False, euler, solver != "euler")
+            coef, euler = K.kdiff_coeffs(cfg_guidance, sigmas, i, first, xl_form=xl_form, semantics=self.scalar_semantics)
+            self.engine.step_kdiff(x, den, old, noise_uc, noise_c, coef, variant, xl_form, euler, solver != "euler")
             have_old = True
             if callback_fn is not None:
                 self._run_callback(callback_fn, i, new_t, den, x)
         return den, x
-
 
     # ------------------------------------------------------------------ ancestral k-diffusion loops
     def _ancestral_loop(self, uc, c, cfg_guidance, cfgpp: bool, two_stage: bool, callback_fn=None, seeds=None):
@@ -504,8 +520,7 @@ class StableDiffusion:
         B = self._batch_of(c, None)
         lam = cfg_guidance
         sigmas = self.tables.karras_sigmas()
-        x = self.initialize_latent(method="random_kdiffusion", latent_dim=(B, self.cfg.out_channels) + self.latent_hw,
-                                   sigmas=sigmas, seeds=seeds).to(torch.float16).contiguous()
+        x = self._kdiff_start((B, self.cfg.out_channels) + self.latent_hw, sigmas, seeds)
         xc, den, uden = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         x2, den2, uden2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         variant = 1 if cfgpp else 0
@@ -569,10 +584,8 @@ class BaseDDIM(StableDiffusion):
         zt = kwargs.get("latents")
         if zt is None:
             zt = self.initialize_latent(latent_dim=(B, self.cfg.out_channels) + self.latent_hw, seeds=kwargs.get("seeds"))
-        z0t, zt = self._ddim_forward(zt.to(self.work_device), uc, c, cfg_guidance, self.cfgpp, callback_fn)
-        if kwargs.get("return_latents"):
-            return z0t, zt
-        return self._finish(z0t)
+        z0t, zt = self._ddim_loop(zt.to(self.work_device), uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn)
+        return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
 @register_solver("euler")
@@ -584,11 +597,11 @@ class EulerCFGSolver(StableDiffusion):
     @controlled
     def sample(self, cfg_guidance, prompt=["", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
-        den, x = self._kdiff_loop(uc, c, cfg_guidance, self.variant, self.solver, callback_fn, kwargs.get("seeds"))
-        out = den if self.solver == "euler" else x      # Euler decodes `denoised`, 2M decodes `x`
-        if kwargs.get("return_latents"):
-            return den, x
-        return self._finish(out)
+        sigmas = self.tables.karras_sigmas()
+        x = self._kdiff_start((int(c.shape[0]), self.cfg.out_channels) + self.latent_hw, sigmas, kwargs.get("seeds"))
+        den, x = self._kdiff_loop(x, sigmas, uc, c, cfg_guidance, self.variant, self.solver, callback_fn)
+        # Euler decodes `denoised`, 2M decodes `x`
+        return self._result(kwargs.get("return_latents"), (den, x), den if self.solver == "euler" else x)
 
 
 @register_solver("euler_a")
@@ -601,9 +614,8 @@ class EulerAncestralCFGSolver(StableDiffusion):
     def sample(self, cfg_guidance, prompt=["", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         den, x = self._ancestral_loop(uc, c, cfg_guidance, self.cfgpp, self.two_stage, callback_fn, kwargs.get("seeds"))
-        if kwargs.get("return_latents"):
-            return den, x
-        return self._finish(x if self.two_stage else den)     # Euler-a decodes `denoised`, 2S-a decodes `x`
+        # Euler-a decodes `denoised`, 2S-a decodes `x`
+        return self._result(kwargs.get("return_latents"), (den, x), x if self.two_stage else den)
 
 
 @register_solver("dpm++_2s_a")
@@ -634,10 +646,8 @@ class InversionDDIM(BaseDDIM):
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         zt = self._invert(src_img, uc, c, cfg_guidance, kwargs)
-        z0t, zt = self._ddim_forward(zt, uc, c, cfg_guidance, self.cfgpp, callback_fn)
-        if kwargs.get("return_latents"):
-            return z0t, zt
-        return self._finish(z0t)
+        z0t, zt = self._ddim_loop(zt, uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn)
+        return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
 @register_solver("ddim_edit")
@@ -650,10 +660,8 @@ class EditWordSwapDDIM(InversionDDIM):
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, src_c, tgt_c = self._embeds(prompt, kwargs, n_cond=2)
         zt = self._invert(src_img, uc, src_c, cfg_guidance, kwargs)
-        z0t, zt = self._ddim_forward(zt, uc, tgt_c, cfg_guidance, self.cfgpp, callback_fn, desc="DDIM-edit")
-        if kwargs.get("return_latents"):
-            return z0t, zt
-        return self._finish(z0t)
+        z0t, zt = self._ddim_loop(zt, uc, tgt_c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn, desc="DDIM-edit")
+        return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
 # ======== CFG++ solvers (renoise with eps_uc; small-lambda regime) ========
@@ -691,21 +699,13 @@ class DPMpp2mCFGppSolver(EulerCFGSolver):
 class InversionDDIMCFGpp(InversionDDIM):
     """CFG++ inversion (x0 from eps_uc, renoise eps_hat) + CFG++ reconstruction
     (reference: latent_diffusion.py:882-957)."""
-    cfgpp = True
-
-    @torch.no_grad()
-    def inversion(self, z0, uc, c, cfg_guidance: float = 1.0):
-        return self._ddim_inversion(z0, uc, c, cfg_guidance, cfgpp=True)
+    cfgpp = inversion_cfgpp = True
 
 
 @register_solver("ddim_edit_cfg++")
 class EditWordSwapDDIMCFGpp(EditWordSwapDDIM):
     """reference: latent_diffusion.py:959-1010."""
-    cfgpp = True
-
-    @torch.no_grad()
-    def inversion(self, z0, uc, c, cfg_guidance: float = 1.0):
-        return self._ddim_inversion(z0, uc, c, cfg_guidance, cfgpp=True)
+    cfgpp = inversion_cfgpp = True
 
 
 if __name__ == "__main__":

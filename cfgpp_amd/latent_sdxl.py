@@ -15,9 +15,8 @@ from typing import Any, Dict, Optional, Tuple
 import torch
 
 from .registry import Registry
-from . import coeffs as K
 from .conditioning import SyntheticTextEncoder, as_list
-from .latent_diffusion import StableDiffusion, _progress, controlled
+from .latent_diffusion import StableDiffusion, controlled
 from .schedule import get_sigmas_karras
 from .unet_config import SDXL as SDXL_CFG
 
@@ -91,35 +90,21 @@ class SDXL(StableDiffusion):
     # ------------------------------------------------------------------ UNet
     def predict_noise(self, zt, t, uc, c, added_cond_kwargs):
         """reference: latent_sdxl.py:167-185."""
-        self._ensure_context(uc, c, added_cond_kwargs)
-        noise_uc, noise_c = self.engine.predict(zt, float(t))
-        if uc is None:
-            return noise_c, noise_c
-        if c is None:
-            return noise_uc, noise_uc
-        return noise_uc, noise_c
+        return self._predict(zt, t, uc, c, added_cond_kwargs)
 
-    def _ensure_context(self, uc, c, added_cond_kwargs):
-        if uc is None and c is None:
-            raise ValueError("predict_noise needs at least one of uc / c")
-        a = c if uc is None else uc
-        b = uc if c is None else c
-        te, ti = added_cond_kwargs["text_embeds"], added_cond_kwargs["time_ids"]
-        key = (a.data_ptr(), b.data_ptr(), te.data_ptr(), ti.data_ptr(), tuple(te.shape), tuple(a.shape), tuple(b.shape),
-               a._version, b._version, te._version, ti._version, self._lora_epoch())
-        changed = getattr(self, "_ctx_key", None) != key
-        if changed:
-            B = max(int(a.shape[0]), int(b.shape[0]))
-            rows = 2 * B
-            # cond rows: 2B ([neg.., pos..]) or B / 1 (positive only -> applied to both halves, quirk Q7)
-            if te.shape[0] not in (rows, B, 1):
-                raise ValueError(f"text_embeds has {te.shape[0]} rows for a UNet batch of {rows}")
-            te_full = te if te.shape[0] == rows else te.repeat(rows // te.shape[0], 1)
-            ti_full = ti if ti.shape[0] == rows else ti.repeat(rows // ti.shape[0], 1)
-            self.engine.set_context(a, b, te_full, ti_full)
-            self._ctx_key = key
-            self._ctx_keep = (a, b, te, ti)
-        self._ensure_image_context(changed, uc, c)
+    def _added_context(self, added):
+        te, ti = added["text_embeds"], added["time_ids"]
+        return (te, ti), (te.data_ptr(), ti.data_ptr(), tuple(te.shape), te._version, ti._version)
+
+    def _set_context(self, uc, c, te, ti):
+        B = max(int(uc.shape[0]), int(c.shape[0]))
+        rows = 2 * B
+        # cond rows: 2B ([neg.., pos..]) or B / 1 (positive only -> applied to both halves, quirk Q7)
+        if te.shape[0] not in (rows, B, 1):
+            raise ValueError(f"text_embeds has {te.shape[0]} rows for a UNet batch of {rows}")
+        te_full = te if te.shape[0] == rows else te.repeat(rows // te.shape[0], 1)
+        ti_full = ti if ti.shape[0] == rows else ti.repeat(rows // ti.shape[0], 1)
+        self.engine.set_context(uc, c, te_full, ti_full)
 
     # ------------------------------------------------------------------ sample
     def _sizes(self, original_size, target_size):
@@ -160,9 +145,7 @@ class SDXL(StableDiffusion):
         self._batch = int(emb.shape[0])
         ret_lat = kwargs.pop("return_latents", False)
         zt = self.reverse_process(null_e, emb, cfg_guidance, add_cond_kwargs, target_size, **kwargs)
-        if ret_lat:
-            return zt
-        return self._finish(zt)
+        return self._result(ret_lat, zt, zt)
 
     # ------------------------------------------------------------------ latents
     def initialize_latent(self, method: str = "random", src_img: Optional[torch.Tensor] = None,
@@ -205,25 +188,11 @@ class SDXL(StableDiffusion):
                 add_cond_kwargs["text_embeds"] = add_cond_kwargs["text_embeds"][-B:]
                 add_cond_kwargs["time_ids"] = add_cond_kwargs["time_ids"][-B:]
 
-    def _inversion_xl(self, z0, uc, c, cfg_guidance, add_cond_kwargs, cfgpp):
-        self._split_cond_for_inversion(cfg_guidance, add_cond_kwargs)
-        zt = self._own_latent(z0)
-        self._ensure_context(uc, c, add_cond_kwargs)
-        done = self._graph_loop(zt, list(reversed(self.scheduler.timesteps)), uc, c, cfg_guidance, cfgpp, False, lambda t: (
-            self.tables.ddim_sqrt_coeffs(t, inversion=True), "tw" if int(t) - self.tables.skip < 0 else None))
-        if done is not None:
-            return done[1]
-        z0t = torch.empty_like(zt)
-        for t in _progress(reversed(self.scheduler.timesteps), "DDIM inversion"):
-            sqrt4 = self.tables.ddim_sqrt_coeffs(t, inversion=True)
-            noise_uc, noise_c = self.predict_noise(zt, t, uc, c, add_cond_kwargs)
-            dev_a = "tw" if int(t) - self.tables.skip < 0 else None      # self.alpha(t - skip) = the DEVICE-resident final alpha
-            self._ddim_update(zt, z0t, noise_uc, noise_c, cfg_guidance, sqrt4, cfgpp, False, dev_a)
-        return zt
-
     def inversion(self, z0, uc, c, cfg_guidance, add_cond_kwargs):
-        """CFG inversion (reference: latent_sdxl.py:301-320)."""
-        return self._inversion_xl(z0, uc, c, cfg_guidance, add_cond_kwargs, cfgpp=False)
+        """CFG / CFG++ inversion (reference: latent_sdxl.py:301-320 / 985-1004)."""
+        self._split_cond_for_inversion(cfg_guidance, add_cond_kwargs)
+        return self._ddim_loop(z0, uc, c, cfg_guidance, self.inversion_cfgpp, False, inversion=True, added=add_cond_kwargs,
+                               desc="DDIM inversion")[1]
 
     def reverse_process(self, *args, **kwargs):
         raise NotImplementedError
@@ -231,55 +200,6 @@ class SDXL(StableDiffusion):
     # ------------------------------------------------------------------ k-diffusion helpers
     def sigma_to_t(self, sigma, quantize=None):
         return self.tables.sigma_to_t(sigma, self.quantize if quantize is None else quantize)
-
-    def _ddim_xl(self, null_e, emb, cfg_guidance, add_cond_kwargs, shape, cfgpp, callback_fn, wrap, zt=None, desc="SDXL",
-                 seeds=None):
-        if zt is None:
-            zt = self.initialize_latent(size=self._latent_size(shape), seeds=seeds)
-        zt = self._own_latent(zt)
-        ts = self.scheduler.timesteps.int() if wrap else self.scheduler.timesteps
-        if callback_fn is None:
-            self._ensure_context(null_e, emb, add_cond_kwargs)
-            done = self._graph_loop(zt, ts, null_e, emb, cfg_guidance, False, cfgpp, lambda t: (
-                self.tables.ddim_sqrt_coeffs(t, wrap=wrap), "rn" if (not wrap and int(t) - self.tables.skip < 0) else None))
-            if done is not None:
-                return done[0]
-        z0t = torch.empty_like(zt)
-        for step, t in enumerate(_progress(ts, desc)):
-            sqrt4 = self.tables.ddim_sqrt_coeffs(t, wrap=wrap)
-            noise_uc, noise_c = self.predict_noise(zt, t, null_e, emb, add_cond_kwargs)
-            dev_a = "rn" if (not wrap and int(t) - self.tables.skip < 0) else None
-            self._ddim_update(zt, z0t, noise_uc, noise_c, cfg_guidance, sqrt4, False, cfgpp, dev_a)
-            if callback_fn is not None:
-                self._run_callback(callback_fn, step, t, z0t, zt)
-        return z0t          # for the last step, do not add noise
-
-    def _kdiff_xl(self, null_e, emb, cfg_guidance, add_cond_kwargs, shape, callback_fn, *, sigmas, n_steps, x0_scale_mode,
-                  input_mode, xl_form, variant, solver, t_of_sigma, ret, seeds=None):
-        size = self._latent_size(shape)
-        if x0_scale_mode == "kdiff":       # randn * sqrt(sigma0^2 + 1) in fp32, then cast (latent_sdxl.py:290-294)
-            x = self.initialize_latent(method="random_kdiffusion", latent_dim=size, sigmas=sigmas, seeds=seeds).to(torch.float16)
-        else:                              # randn cast to fp16, then * sigma0 (latent_sdxl.py:882-884)
-            x = self.initialize_latent(method="random", size=size, seeds=seeds).to(torch.float16)
-            x = x * sigmas[0]
-        x = x.contiguous()
-        xc, den, old = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-        have_old = False
-        for i in _progress(range(n_steps), "SDXL"):
-            sigma = sigmas[i]
-            new_t = t_of_sigma(sigma)
-            if input_mode == 0:
-                self.engine.kdiff_input(x, xc, K.kdiff_input_scale_sd(sigma, self.scalar_semantics), 0)
-            else:
-                self.engine.kdiff_input(x, xc, float(self._alphas_2m[i].clone().sqrt()), 1)
-            noise_uc, noise_c = self.predict_noise(xc, new_t, null_e, emb, add_cond_kwargs)
-            first = (solver == "euler") or (not have_old)
-            coef, euler = K.kdiff_coeffs(cfg_guidance, sigmas, i, first, xl_form=xl_form, semantics=self.scalar_semantics)
-            self.engine.step_kdiff(x, den, old, noise_uc, noise_c, coef, variant, xl_form, euler, solver != "euler")
-            have_old = True
-            if callback_fn is not None:
-                self._run_callback(callback_fn, i, new_t, den, x)
-        return den if ret == "den" else x
 
 
 class SDXLLightning(SDXL):
@@ -306,8 +226,12 @@ class BaseDDIM(SDXL):
 
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):
-        return self._ddim_xl(null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape, self.cfgpp,
-                             callback_fn, wrap=True, zt=kwargs.get("latents"), seeds=kwargs.get("seeds"))
+        zt = kwargs.get("latents")
+        if zt is None:
+            zt = self.initialize_latent(size=self._latent_size(shape), seeds=kwargs.get("seeds"))
+        # unguarded alpha index (quirk Q3); for the last step, do not add noise: z0t
+        return self._ddim_loop(zt, null_prompt_embeds, prompt_embeds, cfg_guidance, False, self.cfgpp, wrap=True,
+                               added=add_cond_kwargs, callback_fn=callback_fn, desc="SDXL")[0]
 
 
 @register_solver("euler")
@@ -319,10 +243,9 @@ class Euler(SDXL):
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):
         sigmas = self.tables.karras_sigmas()
-        return self._kdiff_xl(null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape, callback_fn,
-                              sigmas=sigmas, n_steps=len(self.scheduler.timesteps), x0_scale_mode="kdiff", input_mode=0,
-                              xl_form=False, variant=self.variant, solver="euler", t_of_sigma=self.timestep, ret="den",
-                              seeds=kwargs.get("seeds"))
+        x = self._kdiff_start(self._latent_size(shape), sigmas, kwargs.get("seeds"))
+        return self._kdiff_loop(x, sigmas, null_prompt_embeds, prompt_embeds, cfg_guidance, self.variant, "euler", callback_fn,
+                                added=add_cond_kwargs, desc="SDXL")[0]
 
 
 class _LightningMixin:
@@ -375,9 +298,7 @@ class EditWardSwapDDIM(BaseDDIM):
         self._batch = int(src_e.shape[0])
         ret_lat = kwargs.pop("return_latents", False)
         zt = self.reverse_process(null_e, src_e, tgt_e, cfg_guidance, add_src, add_tgt, **kwargs)
-        if ret_lat:
-            return zt
-        return self._finish(zt)
+        return self._result(ret_lat, zt, zt)
 
     def reverse_process(self, null_prompt_embeds, src_prompt_embeds, tgt_prompt_embed, cfg_guidance,
                         add_src_cond_kwargs, add_tgt_cond_kwargs, callback_fn=None, **kwargs):
@@ -385,8 +306,8 @@ class EditWardSwapDDIM(BaseDDIM):
                                     uc=null_prompt_embeds, c=src_prompt_embeds, cfg_guidance=cfg_guidance,
                                     add_cond_kwargs=add_src_cond_kwargs)
         # forward loop with the TARGET prompt; guarded alpha() here (latent_sdxl.py:679-703), unlike `ddim`
-        return self._ddim_xl(null_prompt_embeds, tgt_prompt_embed, cfg_guidance, add_tgt_cond_kwargs, None, self.cfgpp,
-                             callback_fn, wrap=False, zt=zt)
+        return self._ddim_loop(zt, null_prompt_embeds, tgt_prompt_embed, cfg_guidance, False, self.cfgpp, wrap=False,
+                               added=add_tgt_cond_kwargs, callback_fn=callback_fn, desc="SDXL")[0]
 
 
 # ======== CFG++ solvers (renoise with eps_uc; small-lambda regime) ========
@@ -406,10 +327,9 @@ class EulerCFGpp(SDXL):
         total_sigmas = (1 - self.total_alphas).sqrt() / self.total_alphas.sqrt()
         sigmas = total_sigmas[torch.round(self.scheduler.timesteps.float()).int()]
         sigmas = torch.cat([sigmas, torch.tensor([0.0])])
-        return self._kdiff_xl(null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape, callback_fn,
-                              sigmas=sigmas, n_steps=len(self.scheduler.timesteps), x0_scale_mode="kdiff", input_mode=0,
-                              xl_form=False, variant=1, solver="euler", t_of_sigma=self.timestep, ret="den",
-                              seeds=kwargs.get("seeds"))
+        x = self._kdiff_start(self._latent_size(shape), sigmas, kwargs.get("seeds"))
+        return self._kdiff_loop(x, sigmas, null_prompt_embeds, prompt_embeds, cfg_guidance, 1, "euler", callback_fn,
+                                added=add_cond_kwargs, desc="SDXL")[0]
 
 
 @register_solver("euler_cfg++_lightning")
@@ -439,11 +359,12 @@ class DPMpp2mCFGppSolver(SDXL):
                         callback_fn=None, **kwargs):
         alphas = self.scheduler.alphas_cumprod[self.scheduler.timesteps.int()]
         sigmas = (1 - alphas).sqrt() / alphas.sqrt()
-        self._alphas_2m = alphas
-        return self._kdiff_xl(null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape, callback_fn,
-                              sigmas=sigmas, n_steps=len(self.scheduler.timesteps) - 1, x0_scale_mode="mul", input_mode=1,
-                              xl_form=True, variant=2, solver="dpm2m", t_of_sigma=self.sigma_to_t, ret="x",
-                              seeds=kwargs.get("seeds"))
+        # randn cast to fp16, then * sigma0 (latent_sdxl.py:882-884)
+        x = self.initialize_latent(method="random", size=self._latent_size(shape), seeds=kwargs.get("seeds")).to(torch.float16)
+        x = (x * sigmas[0]).contiguous()
+        return self._kdiff_loop(x, sigmas, null_prompt_embeds, prompt_embeds, cfg_guidance, 2, "dpm2m", callback_fn,
+                                added=add_cond_kwargs, n_steps=len(self.scheduler.timesteps) - 1, alphas=alphas, xl_form=True,
+                                t_of_sigma=self.sigma_to_t, desc="SDXL")[1]
 
 
 @register_solver("dpm++_2m_cfgpp_lightning")
@@ -457,11 +378,7 @@ class DPMpp2mCFGppLightningSolver(_LightningMixin, DPMpp2mCFGppSolver, SDXLLight
 @register_solver("ddim_edit_cfg++")
 class EditWardSwapDDIMCFGpp(EditWardSwapDDIM):
     """CFG++ inversion + CFG++ regeneration (reference: latent_sdxl.py:954-1025)."""
-    cfgpp = True
-
-    @torch.no_grad()
-    def inversion(self, z0, uc, c, cfg_guidance, add_cond_kwargs):
-        return self._inversion_xl(z0, uc, c, cfg_guidance, add_cond_kwargs, cfgpp=True)
+    cfgpp = inversion_cfgpp = True
 
 
 # API symmetry with SD1.5 (BASELINE.json config 5 names "SDXL ddim_inversion_cfg++"): the reference

@@ -436,6 +436,90 @@ def test_sd_ancestral_trajectory(golden, name, tag, lam, monkeypatch):
     assert torch.equal(torch.stack(rec.z0t), T(g[tag + "/z0t"])) and torch.equal(torch.stack(rec.zt), T(g[tag + "/zt"]))
 
 
+# ------------------------------------------------------------------ graph step table == eager loop
+def _with_graph(engine_cls):
+    """``engine_cls`` with the whole-loop entry of the HIP engine: the step table is replayed with predict + step_ddim"""
+    class GraphEngine(engine_cls):
+        graph_enabled = True
+
+        def __init__(self, *args, **kwargs):
+            super().__init__(*args, **kwargs)
+            self.tables = []
+
+        def ddim_loop_graph(self, zt, steps, lam, tweedie_uc, renoise_uc, single=""):
+            self.tables.append(len(steps))
+            z, z0t = zt.clone(), torch.empty_like(zt)
+            for t, *co in steps:
+                euc, ec = self.predict(z, t)
+                if single == "uc":
+                    ec = euc
+                elif single == "c":
+                    euc = ec
+                self.step_ddim(z, z0t, euc, ec, lam, tuple(co), tweedie_uc, renoise_uc)
+            return z0t.clone(), z.clone()
+    return GraphEngine
+
+
+def _inpaint9_unet(z, t, ehs, te, ti):
+    """the scripted UNet on a 9-channel input: mask and masked-image latent enter the 4 predicted channels"""
+    return scripted_unet(z[:, :4] + z[:, 4:5] * z[:, 5:9], t, ehs, te, ti)
+
+
+def _graph_case(case, engine_cls):
+    kind, name, nfe, lam = case
+    p = ["bad", "a cat", "a dog"]
+    z0 = torch.randn(1, 4, 8, 8, generator=torch.Generator().manual_seed(11))
+    if kind == "sd":
+        eng = engine_cls(scripted_unet)
+        s = sd.get_solver(name, solver_config=cfgn(nfe), device="cpu", engine=eng, text_encoder=StubSDText(), latent_hw=(8, 8),
+                          vae=StubVAE(0.18215))
+        kw = dict(latents=zT_sd()) if name.startswith("ddim_cfg") or name == "ddim" else \
+            dict(src_latent=z0.half() if "inversion" in name else z0)
+        out = s.sample(cfg_guidance=lam, prompt=p if "edit" in name else p[:2], return_latents=True, **kw)
+    elif kind == "xl":
+        eng = engine_cls(scripted_unet)
+        s = xl.get_solver(name, solver_config=cfgn(nfe), device="cpu", engine=eng,
+                          text_encoder=(StubXLText("L", 768), StubXLText("G", 1280)), latent_hw=(8, 8), vae=StubVAE(0.13025))
+        edit = "edit" in name
+        kw = dict(src_latent=z0.half()) if edit else dict(seeds=[42])
+        out = s.sample(prompt1=p if edit else p[:2], prompt2=p if edit else p[:2], cfg_guidance=lam, target_size=(64, 64),
+                       original_size=(64, 64), return_latents=True, **kw)
+    else:
+        from cfgpp_amd import inpaint as IP
+        from cfgpp_amd.unet_config import SD15_INPAINT
+        eng = engine_cls(_inpaint9_unet)
+        s = IP.get_inpaint_solver(name, model="sd15", solver_config=cfgn(nfe), device="cpu", unet_config=SD15_INPAINT, engine=eng,
+                                  text_encoder=StubSDText(), latent_hw=(8, 8), vae=StubVAE(0.18215))
+        g = torch.Generator().manual_seed(5)
+        img = torch.rand(1, 3, 64, 64, generator=g) * 2 - 1
+        mask = torch.zeros(1, 1, 64, 64)
+        mask[..., 16:48, 8:40] = 1.0
+        out = s.sample(cfg_guidance=lam, prompt=p[:2], src_img=img, mask=mask, strength=0.75, seeds=[3], return_latents=True)
+    return (out if isinstance(out, tuple) else (out,)), eng
+
+
+@pytest.mark.parametrize("case,tables", [
+    (("sd", "ddim_cfg++", 5, 0.6), [5]), (("sd", "ddim", 4, 7.5), [4]), (("sd", "ddim_inversion_cfg++", 6, 0.6), [6, 6]),
+    (("sd", "ddim_edit", 5, 2.0), [5, 5]),
+    (("xl", "ddim_cfg++", 7, 0.6), [7]), (("xl", "ddim_cfg++_lightning", 4, 1.0), [4]), (("xl", "ddim_edit_cfg++", 5, 0.6), [5, 5]),
+    (("xl", "ddim_edit", 6, 1.0), [6, 6]),
+    (("inpaint", "ddim_inpaint_cfg++", 7, 0.6), [5]),
+], ids=lambda v: "-".join(map(str, v[:2])) if isinstance(v, tuple) else None)
+def test_graph_step_table_replays_the_eager_loop(case, tables):
+    """the step table ``_graph_loop`` hands to ``engine.ddim_loop_graph`` holds exactly what the eager loop hands to
+    ``predict`` / ``step_ddim``: replaying it gives the eager loop's latents, same dtype, bit for bit.  One table for a plain
+    solver, two for invert + regenerate; the 9-channel inpaint solver at strength 0.75 runs int(7 * 0.75) = 5 steps."""
+    from inpaint_mock import InpaintMockEngine
+    base = InpaintMockEngine if case[0] == "inpaint" else MockEngine
+    eager, eng_e = _graph_case(case, base)
+    graph, eng_g = _graph_case(case, _with_graph(base))
+    assert eng_g.tables == tables and len(eng_g.calls) == len(eng_e.calls) == sum(tables)
+    assert [cl["t"] for cl in eng_g.calls] == [cl["t"] for cl in eng_e.calls]
+    assert len(eager) == len(graph)
+    for a, b in zip(eager, graph):
+        assert a.dtype == b.dtype and torch.equal(a, b)
+
+
 def test_product_path_has_no_cpu_fallback():
     from cfgpp_amd._lib import CfgppError
     if torch.cuda.is_available():
