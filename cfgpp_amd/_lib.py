@@ -149,6 +149,9 @@ DEBUG_PROTOTYPES = {
     "cfgpp_attention_set_stagger": (None, [_I]),
     "cfgpp_attention_set_cross": (None, [_I]),
     "cfgpp_attention_last_launch": (None, [C.POINTER(C.c_int)]),
+    "cfgpp_groupnorm_last_launch": (None, [C.POINTER(C.c_int)]),
+    "cfgpp_layernorm_last_launch": (None, [C.POINTER(C.c_int)]),
+    "cfgpp_softmax_last_launch": (None, [C.POINTER(C.c_int)]),
 }
 
 _lib = None

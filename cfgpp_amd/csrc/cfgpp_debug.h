@@ -15,7 +15,7 @@ int cfgpp_op_softmax_rows(void* s, long rows, int ncols, void* stream);
 int cfgpp_op_conv_in_ex(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                         int R, int zB, int Cin, int H, int W, int Cout, const float* pre_w, const float* pre_b,
                         float in_scale, void* stream);
-/* stats: scratch of N*(1024*G*2 + G*2) floats (per-block partials + mean/rstd); deterministic, no atomics */
+/* stats: scratch of N*(1024*G*2 + G*2) floats (per-block {mean, M2} + mean/rstd); deterministic, no atomics */
 int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const float* gamma, const float* beta,
                        float* stats, int N, int H, int W, int C0, int C1, int G, float eps, int silu,
                        int dst_padded, void* stream);
@@ -50,6 +50,15 @@ int cfgpp_op_layernorm(const void* x, void* y, const float* gamma, const float* 
 /* development / A-B switch: token rows each wave of the LayerNorm kernel keeps in flight (0 = by row count, 1 / 2 / 4);
  * the result does not depend on it. */
 void cfgpp_layernorm_set_rows_per_wave(int rpw);
+/* test hooks: what the last call of each op in csrc/norm_kernels.hip dispatched, host-side records zeroed at entry to the op (a
+ * refused call reports zeros).
+ *   groupnorm (cfgpp_op_groupnorm / cfgpp_op_groupnorm_pre): out8 = {form (0 nothing launched, 1 slab kernel, 2 two launches,
+ *     3 producer statistics), NT, MAXCH, gs, cpp of the slab instance (0 otherwise), pix_per_block and nblk of the stats launch
+ *     (form 2), pix_per_block of the apply launch (forms 2 and 3)};
+ *   layernorm: out2 = {MAXV, RPW} of the layernorm_kernel instance;  softmax_rows: out1 = {MAXC}. */
+void cfgpp_groupnorm_last_launch(int* out8);
+void cfgpp_layernorm_last_launch(int* out2);
+void cfgpp_softmax_last_launch(int* out1);
 /* V^T contract of cfgpp_op_attention: vt is [B*heads][dp][tok_pad] with the keys of every 32-key block
  * permuted - key k lives in column (k & ~12) | ((k & 4) << 1) | ((k & 8) >> 1) (bits 2 and 3 swapped), which is
  * how the QKV projection (cfgpp_op_igemm_heads) writes it; and when d % 32 != 0, row d of every matrix holds

@@ -122,7 +122,10 @@ __device__ __forceinline__ f32x2 gelu_erf_pk(f32x2 x) {
 }
 
 // ---- LayerNorm of ONE row held by a wave (layernorm_kernel): lane l holds the 16-byte chunks l, l + 64, ... (8 channels each) of
-// the row; exact two-pass variance.
+// the row; exact two-pass variance.  Every multiply-add is an explicit fmaf: left to the compiler's fp contraction, different
+// (MAXV, RPW) instances of layernorm_kernel fused different products and their outputs differed in the last fp16 bit.  For the
+// same reason the fp32 result is made opaque before its conversion to fp16: some instances folded the conversion into the
+// multiply-add (v_fma_mix*_f16), others converted the fp32 register.
 template <int MAXV>
 __device__ __forceinline__ void ln_row_stats(const half8_t (&raw)[MAXV], int chunks, int C, float eps, int lane,
                                              float (&v)[MAXV][8], float& mean, float& rstd) {
@@ -141,7 +144,7 @@ __device__ __forceinline__ void ln_row_stats(const half8_t (&raw)[MAXV], int chu
     for (int j = 0; j < MAXV; ++j) {
         const bool live = lane + j * 64 < chunks;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { const float d = v[j][k] - mean; sq += live ? d * d : 0.f; }
+        for (int k = 0; k < 8; ++k) { const float d = v[j][k] - mean; sq = live ? fmaf(d, d, sq) : sq; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
@@ -153,6 +156,10 @@ __device__ __forceinline__ half8_t ln_row_affine(const float (&v)[8], float mean
     const float bb[8] = {be[0].x, be[0].y, be[0].z, be[0].w, be[1].x, be[1].y, be[1].z, be[1].w};
     half8_t o;
 #pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = (half_t)((v[k] - mean) * rstd * gg[k] + bb[k]);
+    for (int k = 0; k < 8; ++k) {
+        float f = fmaf((v[k] - mean) * rstd, gg[k], bb[k]);
+        asm volatile("" : "+v"(f));
+        o[k] = (half_t)f;
+    }
     return o;
 }

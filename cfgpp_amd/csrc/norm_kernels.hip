@@ -16,9 +16,10 @@
 //      variance are the exact two-pass form (sum, then sum of squared deviations), like torch.
 //      Used whenever the slab fits 16 x 16-B chunks per thread of a <= 960-thread workgroup (H*W <= 1024 at
 //      every channel count of the two UNets): all 32x32 / 16x16 / 8x8 GroupNorms of SD1.5 and the 32x32 ones of SDXL.
-//  (2) two launches for larger slabs (64x64 and 128x128 levels): per-block partial sums of (x - pivot),
-//      (x - pivot)^2 with a per-(sample, group) pivot = the group's first element, then an apply kernel
-//      whose prologue reduces the partials in a fixed order.  6 B / element.
+//  (2) two launches for larger slabs (64x64 and 128x128 levels): per pixel block and group {mean, M2 = sum of squared
+//      deviations} from sums of (x - pivot), (x - pivot)^2 with the pivot a median of three of the BLOCK's own values, then an apply
+//      kernel whose prologue combines the blocks (parallel variance, two passes over the block pairs) in a fixed order.
+//      6 B / element.
 #include <algorithm>
 #include "common.h"
 
@@ -30,8 +31,9 @@ struct GNArgs {
     half_t* dst;
     const float* gamma;   // [C]
     const float* beta;    // [C]
-    float* stats;         // [N][nblk][G][2] fp32 per-block partial (sum, sumsq) of (x - pivot)
+    float* stats;         // [N][nblk][G][2] fp32 per pixel block and group {mean, M2}
     int nblk;
+    int spb;              // pixels per block of the stats launch (the apply launch has its own pix_per_block)
     int N, H, W;
     int C0, C1;           // channels of src0 / src1 (C = C0 + C1), both multiples of 8
     int G;                // groups
@@ -50,11 +52,17 @@ __device__ __forceinline__ long pad_off(int n, int y, int x, int H, int W) {
     return ((long)(n * (H + 2) + y + 1) * (W + 2) + x + 1);
 }
 
-// pivot of (sample n, group g): the group's first channel at the sample's first pixel (any value within a few
-// sigma of the group mean removes the cancellation; this one costs one L2 hit)
-__device__ __forceinline__ float gn_pivot(const GNArgs& a, int n, int c_first) {
-    const long p = pad_off(n, 0, 0, a.H, a.W);
-    return c_first < a.C0 ? (float)a.src0[p * a.C0 + c_first] : (float)a.src1[p * a.C1 + (c_first - a.C0)];
+// pivot of a group inside one stats block: the median of the group's first channel at the block's first, middle and last pixel
+// (padded pixel offsets p[3]).  Any value near the block's mean removes the cancellation of sum(x^2) - sum(x)^2 / n; this one
+// costs three L2 hits and survives one outlier among the three.  It is one of the block's own n values, so
+// (pivot - mean)^2 <= M2 and the subtraction loses at most log2(n) bits of that one block, and those only when two of the
+// three are outliers that carry the block's whole M2.  (A pivot per (sample, group), the group's first value - the form
+// before - lost the variance of a group of 32768 elements whose first value was an outlier: sigma 0.01 with 60 at pixel
+// (0, 0), tests/norm_cases.py pivot_outlier.)
+__device__ __forceinline__ float gn_pivot(const GNArgs& a, int c_first, const long (&p)[3]) {
+    const half_t* src = c_first < a.C0 ? a.src0 + c_first : a.src1 + (c_first - a.C0);
+    const long Cs = c_first < a.C0 ? a.C0 : a.C1;
+    return __builtin_amdgcn_fmed3f((float)src[p[0] * Cs], (float)src[p[1] * Cs], (float)src[p[2] * Cs]);
 }
 
 // Makes the packed fp16 slab registers opaque between the passes: otherwise the compiler converts every element
@@ -189,7 +197,7 @@ gn_slab_kernel(GNArgs a) {
 
 // ---- (2) two-launch form ---------------------------------------------------------------------------
 // Pass 1: per-(sample, pixel-block) partial sums of (x - pivot), (x - pivot)^2 for every group: each thread sums
-// 8 channels over its pixels, the block combines them through LDS in a fixed order and writes part[n][blk][g][2].
+// 8 channels over its pixels, the block combines them through LDS in a fixed order and writes {mean, M2} to stats[n][blk][g][2].
 __global__ void __launch_bounds__(256)
 gn_stats_kernel(GNArgs a) {
     __shared__ float s_part[256][16];   // [thread][8 sums | 8 sums of squares]
@@ -206,6 +214,7 @@ gn_stats_kernel(GNArgs a) {
     const float invW = 1.0f / (float)a.W;
     const long pbase = (long)n * (a.H + 2) * (a.W + 2) + (a.W + 2) + 1;
     auto poff = [&](int p) -> long { return pbase + p + 2 * (int)(((float)p + 0.5f) * invW); };
+    const long ppv[3] = {poff(p0), poff((p0 + p1) >> 1), poff(p1 - 1)};   // where the block's pivots are read
     float gsum = 0.f, gsq = 0.f;                             // thread g < G owns group g
     for (int cbase = 0; cbase < chunks; cbase += blockDim.x) {
         int chunk, psub;
@@ -221,7 +230,7 @@ gn_stats_kernel(GNArgs a) {
             if (c < a.C0) { src = a.src0; cs = c; Cs = a.C0; } else { src = a.src1; cs = c - a.C0; Cs = a.C1; }
             float pv[8];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) pv[k] = gn_pivot(a, n, ((c + k) / cpg) * cpg);
+            for (int k = 0; k < 8; ++k) pv[k] = gn_pivot(a, ((c + k) / cpg) * cpg, ppv);
             // 4 independent 16-B loads in flight per thread; the per-thread summation order is unchanged
             int p = p0 + psub;
             for (; p + 3 * ppi < p1; p += 4 * ppi) {
@@ -261,7 +270,8 @@ gn_stats_kernel(GNArgs a) {
     }
     if ((int)threadIdx.x < a.G) {
         float* dst = a.stats + (((long)n * gridDim.x + blockIdx.x) * a.G + threadIdx.x) * 2;
-        dst[0] = gsum; dst[1] = gsq;
+        const float dm = gsum / (float)(cpg * (p1 - p0));          // block mean - pivot
+        dst[0] = gn_pivot(a, threadIdx.x * cpg, ppv) + dm; dst[1] = fmaxf(gsq - gsum * dm, 0.f);
     }
 }
 
@@ -311,8 +321,8 @@ gn_finalize_kernel(GNArgs a) {
     }
 }
 
-// Pass 2: apply.  Prologue: the fixed-order reduction of the nblk (<= 256) stats blocks to (mean, rstd) per group,
-// recomputed by every workgroup (16 .. 64 KB of L2 reads).
+// Pass 2: apply.  Prologue: the fixed-order combination of the nblk (<= 256) stats blocks to (mean, rstd) per group,
+// recomputed by every workgroup (2 x 16 .. 64 KB of L2 reads).
 __global__ void __launch_bounds__(256)
 gn_apply_kernel(GNArgs a) {
     __shared__ float s_mean[64], s_rstd[64];
@@ -329,28 +339,41 @@ gn_apply_kernel(GNArgs a) {
             s_mean[threadIdx.x] = mr.x; s_rstd[threadIdx.x] = mr.y;
         }
     } else {
-        // thread (g = t % G, slice = t / G) sums stats blocks slice, slice + NSL, ... (independent loads); thread g then adds
-        // the NSL slices in order: a fixed summation order, one round of memory latency
-        __shared__ float s_ps[8][64][2];
+        // The blocks' {mean, M2} pairs combine as M2 = sum_b (M2_b + n_b (mean_b - mean)^2) with mean = sum_b n_b mean_b / n, taken
+        // relative to block 0's mean (|mean| >> sigma is harmless).  Thread (g = t % G, slice = t / G) sums blocks slice,
+        // slice + NSL, ... (independent loads), every thread then adds the NSL slices of its group in order: a fixed summation
+        // order, two rounds of memory latency (the second hits the L2 lines of the first).
+        __shared__ float s_ps[8][64];
         const int NSL = 256 / a.G < 8 ? 256 / a.G : 8;               // slices (G = 32: 8)
         const int g = threadIdx.x % a.G, sl = threadIdx.x / a.G;
+        const float* st = a.stats + (long)n * a.nblk * a.G * 2;
+        const float n_full = (float)(cpg * a.spb), n_last = (float)(cpg * (HW - (a.nblk - 1) * a.spb));
+        const float inv_cnt = 1.0f / ((float)cpg * (float)HW);
+        const float ref = st[g * 2];
         if (sl < NSL) {
-            float s = 0.f, q = 0.f;
+            float s = 0.f;
+            for (int b = sl; b < a.nblk; b += NSL) s += (b == a.nblk - 1 ? n_last : n_full) * (st[((long)b * a.G + g) * 2] - ref);
+            s_ps[sl][g] = s;
+        }
+        __syncthreads();
+        float tot = 0.f;
+        for (int k = 0; k < NSL; ++k) tot += s_ps[k][g];
+        const float mean = ref + tot * inv_cnt;
+        __syncthreads();                                             // s_ps is rewritten
+        if (sl < NSL) {
+            float q = 0.f;
             for (int b = sl; b < a.nblk; b += NSL) {
-                const float* p = a.stats + (((long)n * a.nblk + b) * a.G + g) * 2;
-                s += p[0]; q += p[1];
+                const float2 mm = *reinterpret_cast<const float2*>(st + ((long)b * a.G + g) * 2);
+                const float d = mm.x - mean;
+                q += mm.y + (b == a.nblk - 1 ? n_last : n_full) * d * d;
             }
-            s_ps[sl][g][0] = s; s_ps[sl][g][1] = q;
+            s_ps[sl][g] = q;
         }
         __syncthreads();
         if ((int)threadIdx.x < a.G) {
-            float s = 0.f, q = 0.f;
-            for (int k = 0; k < NSL; ++k) { s += s_ps[k][g][0]; q += s_ps[k][g][1]; }
-            const float inv_cnt = 1.0f / ((float)cpg * (float)HW);
-            const float dm = s * inv_cnt;                      // mean - pivot
-            float var = q * inv_cnt - dm * dm;                 // benign: |dm| is a few sigma at most
-            var = var < 0.f ? 0.f : var;
-            s_mean[g] = gn_pivot(a, n, g * cpg) + dm; s_rstd[g] = rsqrtf(var + a.eps);
+            float m2 = 0.f;
+            for (int k = 0; k < NSL; ++k) m2 += s_ps[k][g];
+            s_mean[g] = mean; s_rstd[g] = rsqrtf(m2 * inv_cnt + a.eps);
         }
     }
     __syncthreads();
@@ -406,6 +429,10 @@ gn_apply_kernel(GNArgs a) {
 
 int g_gn_mode = 0;        // 0 = auto, 1 = always the two-launch form, 2 = slab kernel whenever the slab fits
 int g_ln_rpw = 0;         // LayerNorm rows per wave: 0 = by row count, 1 / 2 / 4 forced (diagnostics)
+// host-side records of what the last call of each op dispatched (test hooks, cfgpp_debug.h); zeroed at entry to the op
+int g_gn_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // form, NT, MAXCH, gs, cpp, stats pix_per_block, stats nblk, apply pix_per_block
+int g_ln_last[2] = {0, 0};                     // MAXV, RPW
+int g_sm_last[1] = {0};                        // MAXC
 
 template <int MAXCH, int NT>
 void launch_gn_slab(const GNArgs& a, int wgs, hipStream_t s) {
@@ -518,11 +545,13 @@ softmax_rows_kernel(half_t* __restrict__ s, int ncols) {
 extern "C" {
 
 int cfgpp_op_softmax_rows(void* s, long rows, int ncols, void* stream) {
+    g_sm_last[0] = 0;
     CFGPP_REQUIRE(s && rows > 0 && ncols % 8 == 0 && ncols <= 256 * 8 * 8, "softmax_rows: ncols=%d (multiple of 8, <= 16384)", ncols);
     hipStream_t st = (hipStream_t)stream;
     const int need = cdiv(ncols / 8, 256);
     if (need <= 2) hipLaunchKernelGGL(softmax_rows_kernel<2>, dim3(rows), dim3(256), 0, st, (half_t*)s, ncols);
     else hipLaunchKernelGGL(softmax_rows_kernel<8>, dim3(rows), dim3(256), 0, st, (half_t*)s, ncols);
+    g_sm_last[0] = need <= 2 ? 2 : 8;
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -536,10 +565,14 @@ static int g_gn_prestats = 1;
 void cfgpp_groupnorm_set_prestats(int on) { g_gn_prestats = on ? 1 : 0; }
 int cfgpp_groupnorm_prestats_enabled() { return g_gn_prestats; }
 void cfgpp_layernorm_set_rows_per_wave(int rpw) { g_ln_rpw = (rpw == 1 || rpw == 2 || rpw == 4) ? rpw : 0; }
+void cfgpp_groupnorm_last_launch(int* out8) { for (int i = 0; i < 8; ++i) out8[i] = g_gn_last[i]; }
+void cfgpp_layernorm_last_launch(int* out2) { out2[0] = g_ln_last[0]; out2[1] = g_ln_last[1]; }
+void cfgpp_softmax_last_launch(int* out1) { out1[0] = g_sm_last[0]; }
 
 int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const float* gamma, const float* beta,
                        float* stats, int N, int H, int W, int C0, int C1, int G, float eps, int silu,
                        int dst_padded, void* stream) {
+    for (int i = 0; i < 8; ++i) g_gn_last[i] = 0;
     const int C = C0 + C1;
     CFGPP_REQUIRE(G > 0 && G <= 64 && C % G == 0, "groupnorm: C=%d not divisible by G=%d (G<=64)", C, G);
     CFGPP_REQUIRE(C0 % 8 == 0 && C1 % 8 == 0, "groupnorm: C0=%d C1=%d must be multiples of 8", C0, C1);
@@ -549,7 +582,7 @@ int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const floa
     a.src0 = (const half_t*)src0; a.src1 = (const half_t*)src1; a.dst = (half_t*)dst;
     a.gamma = gamma; a.beta = beta;
     a.N = N; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.G = G; a.eps = eps; a.silu = silu;
-    a.dst_padded = dst_padded; a.stats = stats; a.nblk = 0; a.gs = 1; a.pix_per_block = 0;
+    a.dst_padded = dst_padded; a.stats = stats; a.nblk = 0; a.spb = 0; a.gs = 1; a.pix_per_block = 0;
     a.gst0 = nullptr; a.gst1 = nullptr; a.pre = 0;
     const int HW = H * W;
     const int cpg = C / G;
@@ -583,6 +616,8 @@ int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const floa
                 }
                 GN_SLAB(320) GN_SLAB(640) GN_SLAB(960)
 #undef GN_SLAB
+                g_gn_last[0] = 1; g_gn_last[1] = nt; g_gn_last[2] = cpt <= 2 ? 2 : cpt <= 4 ? 4 : cpt <= 8 ? 8 : 16;
+                g_gn_last[3] = gs; g_gn_last[4] = cpp;
                 CFGPP_HIP_CHECK(hipGetLastError());
                 return 0;
             }
@@ -593,7 +628,7 @@ int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const floa
     const int nblk_max = std::max(64, std::min(256, cdiv(768, N)));
     int ppb = 16;
     while (cdiv(HW, ppb) > nblk_max) ppb <<= 1;
-    a.pix_per_block = ppb;
+    a.pix_per_block = ppb; a.spb = ppb;
     a.nblk = cdiv(HW, ppb);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(a.nblk, N), dim3(256), 0, s, a);
     // apply: aim for >= ~1024 blocks of >= 16 pixels
@@ -602,6 +637,7 @@ int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const floa
     while (apb > 16 && (long)N * cdiv(HW, apb) < 1024) apb >>= 1;
     b.pix_per_block = apb;
     hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(HW, apb), N), dim3(256), 0, s, b);
+    g_gn_last[0] = 2; g_gn_last[5] = ppb; g_gn_last[6] = a.nblk; g_gn_last[7] = apb;
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -613,6 +649,7 @@ int cfgpp_op_groupnorm(const void* src0, const void* src1, void* dst, const floa
 int cfgpp_op_groupnorm_pre(const void* src0, const void* src1, void* dst, const float* gamma, const float* beta,
                            const float* gst0, const float* gst1, float* stats, int N, int H, int W, int C0, int C1, int G,
                            float eps, int silu, int dst_padded, void* stream) {
+    for (int i = 0; i < 8; ++i) g_gn_last[i] = 0;
     const int C = C0 + C1;
     CFGPP_REQUIRE(G > 0 && G <= 64 && C % G == 0, "groupnorm_pre: C=%d not divisible by G=%d (G<=64)", C, G);
     CFGPP_REQUIRE(C0 % 8 == 0 && C1 % 8 == 0, "groupnorm_pre: C0=%d C1=%d must be multiples of 8", C0, C1);
@@ -623,7 +660,7 @@ int cfgpp_op_groupnorm_pre(const void* src0, const void* src1, void* dst, const 
     a.src0 = (const half_t*)src0; a.src1 = (const half_t*)src1; a.dst = (half_t*)dst;
     a.gamma = gamma; a.beta = beta;
     a.N = N; a.H = H; a.W = W; a.C0 = C0; a.C1 = C1; a.G = G; a.eps = eps; a.silu = silu;
-    a.dst_padded = dst_padded; a.stats = stats; a.nblk = 0; a.gs = 1;
+    a.dst_padded = dst_padded; a.stats = stats; a.nblk = 0; a.spb = 0; a.gs = 1;
     a.gst0 = gst0; a.gst1 = gst1; a.pre = 1;
     const int HW = H * W;
     hipLaunchKernelGGL(gn_finalize_kernel, dim3(G, N), dim3(256), 0, s, a);
@@ -631,12 +668,14 @@ int cfgpp_op_groupnorm_pre(const void* src0, const void* src1, void* dst, const 
     while (apb > 16 && (long)N * cdiv(HW, apb) < 1024) apb >>= 1;
     a.pix_per_block = apb;
     hipLaunchKernelGGL(gn_apply_kernel, dim3(cdiv(HW, apb), N), dim3(256), 0, s, a);
+    g_gn_last[0] = 3; g_gn_last[7] = apb;
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
 
 int cfgpp_op_layernorm(const void* x, void* y, const float* gamma, const float* beta, long rows, int C,
                        float eps, void* stream) {
+    g_ln_last[0] = 0; g_ln_last[1] = 0;
     CFGPP_REQUIRE(C % 8 == 0 && C <= 64 * 8 * 4, "layernorm: C=%d must be a multiple of 8 and <= 2048", C);
     CFGPP_REQUIRE(x && y && gamma && beta && rows > 0, "layernorm: bad args");
     hipStream_t s = (hipStream_t)stream;
@@ -650,6 +689,7 @@ int cfgpp_op_layernorm(const void* x, void* y, const float* gamma, const float* 
     else if (need <= 2) LN_BY_RPW(2);
     else if (need <= 3) LN_BY_RPW(3);
     else LN_LAUNCH(4, 1);
+    g_ln_last[0] = need <= 3 ? need : 4; g_ln_last[1] = need <= 3 ? (rpw >= 4 ? 4 : rpw == 2 ? 2 : 1) : 1;
 #undef LN_BY_RPW
 #undef LN_LAUNCH
     CFGPP_HIP_CHECK(hipGetLastError());

@@ -109,38 +109,75 @@ def conv1x1_2src(x0_pn, x1_pn, w, bias):
     return out
 
 
-def groupnorm(x0_pn, x1_pn, gamma, beta, G, eps, silu, dst_padded=True):
+def _norm_dst(out, N, H, W, C, dst_padded):
+    """the destination of a GroupNorm: a fresh one, or `out` - a contiguous fp16 device tensor [N, H+2, W+2, C] (halo-padded) or
+    [N*H*W, C] (token-major) to write into (tests that watch what the kernel leaves untouched)"""
+    shape = (N, H + 2, W + 2, C) if dst_padded else (N * H * W, C)
+    if out is None:
+        return empty_pn(N, H, W, C) if dst_padded else torch.empty(shape, dtype=torch.float16, device=DEV)
+    assert out.is_contiguous() and out.dtype == torch.float16 and tuple(out.shape) == shape
+    return out
+
+
+def groupnorm(x0_pn, x1_pn, gamma, beta, G, eps, silu, dst_padded=True, out=None):
     N, Hp, Wp, C0 = x0_pn.shape
     H, W = Hp - 2, Wp - 2
     C1 = 0 if x1_pn is None else x1_pn.shape[3]
     C = C0 + C1
     stats = torch.zeros(N * (1024 * G * 2 + G * 2), dtype=torch.float32, device=DEV)
-    if dst_padded:
-        dst = empty_pn(N, H, W, C)
-    else:
-        dst = torch.empty((N * H * W, C), dtype=torch.float16, device=DEV)
+    dst = _norm_dst(out, N, H, W, C, dst_padded)
     check(lib().cfgpp_op_groupnorm(P(x0_pn), P(x1_pn), P(dst), P(gamma), P(beta), P(stats), N, H, W, C0, C1, G,
                                    float(eps), int(silu), int(dst_padded), stream()), "cfgpp_op_groupnorm")
     return dst
 
 
-def groupnorm_pre(x0_pn, x1_pn, gst0, gst1, gamma, beta, G, eps, silu, dst_padded=True):
+def groupnorm_pre(x0_pn, x1_pn, gst0, gst1, gamma, beta, G, eps, silu, dst_padded=True, out=None):
     """GroupNorm with the statistics its inputs' producers left behind (cfgpp_op_igemm_set_gstat)"""
     N, Hp, Wp, C0 = x0_pn.shape
     H, W = Hp - 2, Wp - 2
     C1 = 0 if x1_pn is None else x1_pn.shape[3]
     stats = torch.zeros(N * G * 2, dtype=torch.float32, device=DEV)
-    dst = empty_pn(N, H, W, C0 + C1) if dst_padded else torch.empty((N * H * W, C0 + C1), dtype=torch.float16, device=DEV)
+    dst = _norm_dst(out, N, H, W, C0 + C1, dst_padded)
     check(lib().cfgpp_op_groupnorm_pre(P(x0_pn), P(x1_pn), P(dst), P(gamma), P(beta), P(gst0), P(gst1), P(stats), N, H, W, C0, C1, G,
                                        float(eps), int(silu), int(dst_padded), stream()), "cfgpp_op_groupnorm_pre")
     return dst
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
-    y = torch.empty_like(x)
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
+    y = torch.empty_like(x) if out is None else out
+    assert y.is_contiguous() and y.dtype == torch.float16 and y.shape == x.shape
     check(lib().cfgpp_op_layernorm(P(x), P(y), P(gamma), P(beta), x.shape[0], x.shape[1], float(eps), stream()),
           "cfgpp_op_layernorm")
     return y
+
+
+def softmax_rows(s):
+    """row softmax of the contiguous fp16 device tensor s [rows, ncols], in place"""
+    assert s.is_contiguous() and s.dtype == torch.float16 and s.dim() == 2
+    check(lib().cfgpp_op_softmax_rows(P(s), s.shape[0], s.shape[1], stream()), "cfgpp_op_softmax_rows")
+    return s
+
+
+def _last_launch(name, n):
+    import ctypes
+    out = (ctypes.c_int * n)()
+    getattr(lib(), name)(out)
+    return tuple(out)
+
+
+def groupnorm_last_launch():
+    """(form, NT, MAXCH, gs, cpp, stats pix_per_block, stats nblk, apply pix_per_block) of the last GroupNorm call (cfgpp_debug.h)"""
+    return _last_launch("cfgpp_groupnorm_last_launch", 8)
+
+
+def layernorm_last_launch():
+    """(MAXV, RPW) of the last cfgpp_op_layernorm call"""
+    return _last_launch("cfgpp_layernorm_last_launch", 2)
+
+
+def softmax_last_launch():
+    """(MAXC,) of the last cfgpp_op_softmax_rows call"""
+    return _last_launch("cfgpp_softmax_last_launch", 1)
 
 
 def heads_project(a, w, B, tokens, C, nheads, part0, nparts, q_pad, k_pad):
