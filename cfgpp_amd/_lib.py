@@ -87,6 +87,11 @@ IP_ADAPTER_PROTOTYPES = {
     "cfgpp_unet_image_context": (_I, [_P, _P, _I, _I, _F, _P]),
 }
 
+# the long-prompt extension header (include/cfgpp_long_prompt.h)
+LONG_PROMPT_PROTOTYPES = {
+    "cfgpp_unet_set_max_tokens": (_I, [_P, _I]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_softmax_rows": (_I, [_P, _L, _I, _P]),
@@ -103,6 +108,8 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_layernorm": (_I, [_P, _P, _P, _P, _L, _I, _F, _P]),
     "cfgpp_op_attention_prepare_vt": (_I, [_P, _I, _I, _I, _P]),
     "cfgpp_op_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_attention_cross": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_attention_set_cross_long": (None, [_I]),
     "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -173,7 +180,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

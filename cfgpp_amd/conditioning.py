@@ -12,6 +12,7 @@ can be passed to ``sample(prompt_embeds=...)`` to bypass it entirely.
 from __future__ import annotations
 
 import hashlib
+import re
 from typing import List, Optional, Tuple
 
 import torch
@@ -37,9 +38,35 @@ class SyntheticTextEncoder:
         h = torch.stack(hs).to(torch.float16)
         return h, (torch.stack(pooled).to(torch.float16) if self.pooled_dim else None)
 
+    @property
+    def tok(self):
+        """the tokenizer the chunked prompts (cfgpp_amd.prompt) are cut with: the vocabulary-free one"""
+        if getattr(self, "_tok", None) is None:
+            self._tok = HashTokenizer()
+        return self._tok
+
+    def encode_ids(self, ids: torch.Tensor, clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """ids [n, 77] -> (hidden [n, 77, D], pooled): the same distribution as ``__call__``, seeded from the id row (a chunk of a
+        long prompt has no prompt string of its own; ``__call__`` stays seeded by the text, so with this encoder a one-chunk prompt
+        under ``max_prompt_chunks`` > 1 does NOT give the default path's tensors).  There is one hidden state: ``clip_skip`` is
+        refused, as ``SDXL._text_embed`` refuses it for this encoder on the default path."""
+        if clip_skip is not None:
+            raise NotImplementedError(f"clip_skip={clip_skip}: text encoder {type(self).__name__} returns one hidden state only")
+        hs, pooled = [], []
+        for row in ids.tolist():
+            g = torch.Generator().manual_seed(_seed(",".join(str(int(i)) for i in row), self.tag + "/ids"))
+            hs.append(torch.randn((self.tokens, self.hidden_dim), generator=g) * 0.5)
+            if self.pooled_dim:
+                pooled.append(torch.randn((self.pooled_dim,), generator=g) * 0.5)
+        h = torch.stack(hs).to(torch.float16)
+        return h, (torch.stack(pooled).to(torch.float16) if self.pooled_dim else None)
+
 
 def as_list(p) -> List[str]:
     return [p] if isinstance(p, str) else list(p)
+
+
+_HASH_WORDS = re.compile(r"[a-z0-9]+|[^\sa-z0-9]")      # the word pieces of HashTokenizer: __call__ and encode split alike
 
 
 class HashTokenizer:
@@ -54,11 +81,14 @@ class HashTokenizer:
         self.pad_id = self.EOS if pad_id is None else pad_id
         self.length = length
 
+    def encode(self, text: str) -> List[int]:
+        """ids of one prompt without BOS / EOS / padding and without the cut at 75: what ``__call__`` would produce"""
+        return [_seed(w, "tok") % 49406 for w in _HASH_WORDS.findall(text.lower())]
+
     def __call__(self, prompts: List[str]) -> torch.Tensor:
-        import re
         out = torch.full((len(prompts), self.length), self.pad_id, dtype=torch.long)
         for i, p in enumerate(prompts):
-            words = re.findall(r"[a-z0-9]+|[^\sa-z0-9]", p.lower())[: self.length - 2]
+            words = _HASH_WORDS.findall(p.lower())[: self.length - 2]
             ids = [self.BOS] + [_seed(w, "tok") % 49406 for w in words] + [self.EOS]
             out[i, : len(ids)] = torch.tensor(ids)
         return out
@@ -234,7 +264,15 @@ class ClipTextTower:
     @torch.no_grad()
     def __call__(self, prompts: List[str], clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
         """``clip_skip`` (SDXL only): ``hidden_states[-(clip_skip + 2)]`` instead of ``[-2]`` (latent_sdxl.py:88-92)."""
-        ids = self.tok(prompts).to(self.device)
+        return self.encode_ids(self.tok(prompts), clip_skip)
+
+    max_batch = 8           # chunk rows per model call of ``prompt.encode_prompts``
+
+    @torch.no_grad()
+    def encode_ids(self, ids: torch.Tensor, clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """ids [n, 77] (``[BOS] + ids + [EOS] + pad``) -> (hidden [n,77,D] fp16, pooled [n,P] fp16 | None): ``__call__`` after the
+        tokenizer"""
+        ids = ids.to(self.device)
         out = self.model(input_ids=ids, output_hidden_states=True)
         if clip_skip is not None:
             if not self.penultimate:

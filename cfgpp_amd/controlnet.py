@@ -89,7 +89,7 @@ class HipControlNet:
     UNet of the same geometry (``HipUNet.attach_control``)."""
 
     def __init__(self, cfg: UNetConfig, max_rows: int, sample_hw: Optional[Tuple[int, int]] = None, device: int = 0,
-                 embed_channels: Tuple[int, ...] = EMBED_CHANNELS):
+                 embed_channels: Tuple[int, ...] = EMBED_CHANNELS, max_tokens: int = 77):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise CfgppError("HipControlNet needs a ROCm GPU; the HIP path has no CPU fallback")
@@ -111,6 +111,9 @@ class HipControlNet:
             raise CfgppError("cfgpp_unet_create (ControlNet) failed: " + _lib.last_error())
         self._keep = {}
         self.finalized = False
+        self.max_tokens = 77
+        if int(max_tokens) != 77:      # the UNet's: both see the same text context
+            self.set_max_tokens(max_tokens)
         self.rows = 0
         self.image_rows = 0
 
@@ -140,6 +143,12 @@ class HipControlNet:
             items = items.items()
         for k, v in items:
             self.load_tensor(k, v)
+        return self
+
+    def set_max_tokens(self, max_tokens: int):
+        """before ``finalize``: the longest text context, 77 * j with j <= 4 (include/cfgpp_long_prompt.h: cfgpp_unet_set_max_tokens)"""
+        check(self.lib.cfgpp_unet_set_max_tokens(self._h, int(max_tokens)), "cfgpp_unet_set_max_tokens (ControlNet)")
+        self.max_tokens = int(max_tokens)
         return self
 
     def finalize(self):
@@ -207,7 +216,8 @@ class HipControlNet:
         return float(self.lib.cfgpp_unet_device_bytes(self._h))
 
 
-def build_controlnet(spec, cfg: UNetConfig, max_rows: int, latent_hw: Tuple[int, int], device: int = 0, seed: int = 0) -> HipControlNet:
+def build_controlnet(spec, cfg: UNetConfig, max_rows: int, latent_hw: Tuple[int, int], device: int = 0, seed: int = 0,
+                     max_tokens: int = 77) -> HipControlNet:
     """``spec``: "synthetic" (seeded weights), a path (a diffusers ``controlnet/`` folder or a safetensors file) or a state dict"""
     if isinstance(spec, HipControlNet):
         return spec
@@ -219,4 +229,4 @@ def build_controlnet(spec, cfg: UNetConfig, max_rows: int, latent_hw: Tuple[int,
         cfg = cn_cfg
     else:
         items = spec.items() if isinstance(spec, dict) else spec
-    return HipControlNet(cfg, max_rows=max_rows, sample_hw=latent_hw, device=device).load_state_dict(items).finalize()
+    return HipControlNet(cfg, max_rows=max_rows, sample_hw=latent_hw, device=device, max_tokens=max_tokens).load_state_dict(items).finalize()

@@ -729,6 +729,199 @@ xattn64_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, i
     }
 }
 
+// ---- cross-attention, dp = 64, 129 .. 320 keys (long prompts: 2 .. 4 chunks of 77 text tokens) --------------------------
+// The flash loop reloads the head's K / V^T (48 - 80 KB) for every 128 queries and pays a pipeline prologue and a barrier per
+// tile.  Here, as in xattn64_kernel, a workgroup loads K and V^T ONCE - ntiles = ceil(nk / 64) <= 5 tiles of (K | V^T), 16 KB each,
+// by LDS-DMA in the layouts of attn64_kernel (source-side XOR swizzle, permuted V^T keys); the K half-tile of a 32-key sub-tile that
+// lies wholly beyond nk_valid is not loaded (V^T rows span the whole 64-key tile and are loaded whole; such a sub-tile is never
+// multiplied) - and after one wait and one barrier walks xqb blocks of 128 queries with no further barrier, the next block's Q
+// prefetched.  The scores of 320 keys do not fit in registers, so inside a query block the resident tiles are walked with the
+// online softmax of attn64_kernel: scores in the log2 domain from the pre-scaled fp16 Q, the accumulator of S^T initialised with
+// -m_ref, P rounded to fp16 from the accumulator registers into the PV MFMA, the denominator through the ones row of V^T
+// (d % 32 != 0) or an fp32 sum.  The running maximum uses the DEFERRED RE-REFERENCE of the flash loop (RESCALE_THR), not an exact
+// running max.  Keys >= nk_valid are masked in the last partial 32-key sub-tile; nothing read from slots >= nk_valid reaches the
+// result as long as it is finite (masked P = 0 meets it in the PV product).
+// LDS: ntiles x 16 KB (48 KB at 154 keys: three workgroups per CU; 64 KB at 231, 80 KB at 308: two).
+// Registers (gfx950, register allocation aimed at three waves per SIMD, what 48 KB of LDS allows): <3, ONES> 135 VGPRs,
+// <4, ONES> 144, <4, fp32 sum> 142; no AGPRs, no scratch, 3 waves / SIMD.  The 128 that a fourth wave would need are not reached
+// (the prefetched raw Q next to the scaled Q costs 16 registers) and would buy nothing: LDS caps a CU at three workgroups.
+template <int D16, bool ONES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
+xattn64_long_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, int nxb /* workgroups per batch*head */) {
+    constexpr int DP = 64, DT = 2, TILE = 64 * 128;
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // (K tile t | V^T tile t) for t = 0 .. ntiles - 1
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    int xb, bh;
+    {   // XCD-contiguous (batch*head, chunk) order as attn_block_map
+        const int T = gridDim.x, bid = blockIdx.x;
+        const int q = T >> 3, r = T & 7, xcd = bid & 7, idx = bid >> 3;
+        const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        bh = w / nxb; xb = w - bh * nxb;
+    }
+    const half_t* Qb = a.q + (long)bh * a.q_tok_pad * DP;
+    const half_t* Kb = a.k + (long)bh * a.k_tok_pad * DP;
+    const half_t* Vb = a.vt + (long)bh * DP * a.k_tok_pad;
+    const int ntiles = (a.nk_valid + 63) >> 6;               // 3 .. 5
+    const int nsub = (a.nk_valid + 31) >> 5;                 // 32-key sub-tiles with at least one valid key
+    {
+        const int r8 = lane >> 3, pc = lane & 7;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            if (t < ntiles) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int row = wid * 16 + h * 8 + r8;
+                    const int lc = pc ^ ((row >> 1) & 7);
+                    if (t * 64 + wid * 16 < nsub * 32)         // (wave-uniform) K rows of a sub-tile with a valid key
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (long)(t * 64 + row) * DP + lc * 8),
+                                                         (__attribute__((address_space(3))) void*)(smem + t * 2 * TILE + (wid * 16 + h * 8) * 128), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (long)row * a.k_tok_pad + t * 64 + lc * 8),
+                                                     (__attribute__((address_space(3))) void*)(smem + t * 2 * TILE + TILE + (wid * 16 + h * 8) * 128), 16, 0, 0);
+                }
+            }
+        }
+    }
+    const int fsw = (l31 >> 1) & 7;
+    const int frow = l31 * 128;
+    const int b = bh / a.heads, head = bh - b * a.heads;
+    const int tailv = a.nk_valid & 31;                       // != 0: the last sub-tile is partially masked
+    // first block's Q while the DMA is in flight
+    half8_t qf[D16];
+    int q0 = (xb * xqb) * 128 + wid * 32;
+#pragma unroll
+    for (int ks = 0; ks < D16; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(Qb + (long)(q0 + l31) * DP + ks * 16 + hi * 8);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int blk = 0; blk < xqb; ++blk) {
+        half8_t qs[D16];
+#pragma unroll
+        for (int ks = 0; ks < D16; ++ks)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qs[ks][j] = (half_t)((float)qf[ks][j] * a.scale_log2e);
+        const int qrow = q0 + l31;
+        // next block's Q (clamped: the last block re-reads itself)
+        const int q0n = blk + 1 < xqb ? q0 + 128 : q0;
+#pragma unroll
+        for (int ks = 0; ks < D16; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(Qb + (long)(q0n + l31) * DP + ks * 16 + hi * 8);
+
+        f32x16 oacc[DT];
+        f32x16 negm;                 // -m_ref over the 16 accumulator registers (C operand of the first S^T MFMA of a sub-tile)
+        float l_run = 0.f;           // only used when !ONES
+#pragma unroll
+        for (int r = 0; r < 16; ++r) negm[r] = 0.f;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
+
+        for (int t = 0; t < ntiles; ++t) {
+            const char* Ks = smem + t * 2 * TILE;
+            const char* Vs = Ks + TILE;
+            const int nkt = nsub - 2 * t >= 2 ? 2 : 1;       // (wave-uniform) sub-tiles of this tile with a valid key
+            // ---- S^T - m = K Q^T + (-m) for up to two 32-key sub-tiles (log2 domain) ----
+            f32x16 s[2];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                if (kt < nkt) {
+#pragma unroll
+                    for (int ks = 0; ks < D16; ++ks) {
+                        const half8_t kf = *reinterpret_cast<const half8_t*>(Ks + kt * 32 * 128 + frow + ((((ks << 1) | hi) ^ fsw) << 4));
+                        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qs[ks], ks == 0 ? negm : s[kt], 0, 0, 0);
+                    }
+                    if (tailv != 0 && 2 * t + kt == nsub - 1) {          // (wave-uniform) the one sub-tile with invalid keys
+                        const int nv = tailv - 4 * hi;                   // its valid keys, seen from this half-wave
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) s[kt][r] = ((r & 3) + 8 * (r >> 2)) < nv ? s[kt][r] : -INFINITY;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[kt][r] = -INFINITY;   // no valid key: neither loaded nor multiplied
+                }
+            }
+            // ---- online softmax (deferred re-reference, as attn64_kernel) ----
+            float mx = s[0][0];                      // tile max RELATIVE to m_ref
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            if (t == 0 || !__all(mx <= RESCALE_THR)) {   // (rare after the first tile) re-reference: exact
+                const float delta = t == 0 ? mx : fmaxf(mx, 0.f);
+                const float alpha = __builtin_amdgcn_exp2f(-delta);         // O = 0 on the first tile: alpha irrelevant
+                l_run *= alpha;
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) negm[r] -= delta;
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[kt][r] -= delta;
+            }
+            float psum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __builtin_amdgcn_exp2f(s[kt][r]);
+                    s[kt][r] = pv;
+                    if constexpr (!ONES) psum += pv;
+                }
+            if constexpr (!ONES) l_run += psum;
+            // ---- O^T += V^T P^T ----
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                if (kt < nkt) {
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) {
+                        half8_t pf;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) pf[j] = (half_t)s[kt][8 * tt + j];
+                        const int lc = kt * 4 + 2 * tt + hi;               // logical 16-B chunk of the (permuted) key axis
+#pragma unroll
+                        for (int i = 0; i < DT; ++i) {
+                            const half8_t vf = *reinterpret_cast<const half8_t*>(Vs + i * 32 * 128 + frow + ((lc ^ fsw) << 4));
+                            oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[i], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        // ---- finalize: O = O^T / l, store token-major ----
+        float l_tot;
+        if constexpr (ONES) {
+            const int dr = a.d & 31;
+            float lv = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) if (dr == 8 * g) lv = oacc[DT - 1][4 * g];
+            l_tot = __shfl(lv, l31);
+        } else {
+            l_tot = l_run + __shfl_xor(l_run, 32);
+        }
+        const float inv_l = 1.0f / l_tot;
+        if (qrow < a.nq) {
+            half_t* orow = a.o + ((long)b * a.nq + qrow) * a.o_ld + head * a.d;
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int dd = i * 32 + 8 * g + 4 * hi;
+                    if (dd < a.d) {
+                        half4_t o;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) o[k] = (half_t)(oacc[i][4 * g + k] * inv_l);
+                        *reinterpret_cast<half4_t*>(orow + dd) = o;
+                    }
+                }
+        }
+        q0 = q0n;
+    }
+}
+
 template <int D16, bool ONES, int NST, int WPE = 3>
 int launch_attn64(const AttnArgs& a, dim3 grid, hipStream_t s) {
     constexpr int smem = NST * 2 * 64 * 128;
@@ -845,10 +1038,13 @@ static int g_attn_dma = 1;       // dp = 64: 1 = LDS-DMA kernel, 0 = register-st
                                  // tile t+1 and PV of tile t-1 issued between slices of tile t's softmax, two workgroups per CU - was +6..11 %
                                  // alone, neutral per forward and no better in matrix-pipe utilisation: commit 926a7ad)
 static int g_attn_cross = 1;     // dp = 64, <= 128 keys: 1 = the resident-K/V cross-attention kernel, 0 = the flash loop (A/B switch)
+static int g_attn_cross_long = 1;   // dp = 64, 129 .. 320 keys through cfgpp_op_attention_cross: 0 = the flash loop, 1 = xattn64_long_kernel for the classes
+                                    // it measured >= 3 % faster in (d <= 48, or nk <= 192: see cfgpp_op_attention_cross), 2 = for every shape in its scope (tests, A/B)
 static int g_attn_stagger = 0;   // attn64_kernel: phase shift between the workgroups of a CU, in 64-cycle sleeps per slot (0 = off)
 // what the last cfgpp_op_attention / cfgpp_op_attention_ip call dispatched (host-side record, test hook): {kernel, D16, ONES, xqb};
 // kernel 0 = nothing launched (refused), 1 = attn_kernel, 2 = attn64_kernel, 3 = xattn64_kernel, 4 = xattn64_kernel IP form,
-// 5 = attn_ip_add_kernel (the last launch of the two-pass form); xqb = 0 for the flash kernels and for 5
+// 5 = attn_ip_add_kernel (the last launch of the two-pass form), 6 = xattn64_long_kernel (cfgpp_op_attention_cross); xqb = 0 for the
+// flash kernels and for 5
 static int g_attn_last[4] = {0, 0, 0, 0};
 static void attn_note(int kernel, int d16, int ones, int xqb) {
     g_attn_last[0] = kernel; g_attn_last[1] = d16; g_attn_last[2] = ones; g_attn_last[3] = xqb;
@@ -859,6 +1055,7 @@ extern "C" {
 void cfgpp_attention_set_dma(int mode) { g_attn_dma = mode ? 1 : 0; }
 void cfgpp_attention_set_stagger(int sleeps) { g_attn_stagger = sleeps > 0 ? sleeps : 0; }
 void cfgpp_attention_set_cross(int on) { g_attn_cross = on ? 1 : 0; }
+void cfgpp_attention_set_cross_long(int mode) { g_attn_cross_long = mode < 0 ? 0 : mode > 2 ? 2 : mode; }
 void cfgpp_attention_last_launch(int* out4) { for (int i = 0; i < 4; ++i) out4[i] = g_attn_last[i]; }
 
 // V^T contract: when d is not a multiple of 32, row d of every [dp][tok_pad] matrix must hold ones (softmax
@@ -947,6 +1144,58 @@ int cfgpp_op_attention(const void* q, const void* k, const void* vt, void* o, in
 #undef ATTN_CASE
     CFGPP_HIP_CHECK(hipGetLastError());
     attn_note(1, d16, ones, 0);
+    return 0;
+}
+
+// Cross-attention of the UNet: cfgpp_op_attention, except where xattn64_long_kernel (record: kernel 6) is taken.  Its scope is
+// dp = 64 with 129 .. 320 keys (a text context of 2 .. 4 chunks of 77 tokens); what SHIPS (mode 1, the default) is the part of
+// that scope where the interleaved per-launch A/B against the flash loop on the MI355X gave >= 3 % (the in-situ tuner's threshold
+// for a pin; profiles/long_prompt/launch_ab.jsonl, run-to-run spreads <= 3 %): D16 = 3 (d = 40, 48) at every key count (-11.9 %
+// at 154 keys, -3.9 % at 231, -3.4 % at 308) and D16 = 4 (d = 56, 64) at up to three resident tiles, nk <= 192 (-3.2 % at
+// Nq = 4096, -7.2 % at 1024).  Not shipped: D16 = 4 at four / five tiles (+11 .. +16 %: two 64 - 80 KB workgroups per CU hide less
+// latency than the flash loop's four).  Mode 2 takes the whole scope.  Every other shape is forwarded: same launch, same bits,
+// same record.
+int cfgpp_op_attention_cross(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d,
+                             int nq, int nk, int q_tok_pad, int k_tok_pad, void* stream) {
+    const int dt = (d + 31) / 32;
+    const bool scope = dt == 2 && g_attn_dma && g_attn_cross && nk >= 129 && nk <= 320;
+    const bool measured = (d + 15) / 16 == 3 || nk <= 192;
+    if (!(scope && (g_attn_cross_long == 2 || (g_attn_cross_long == 1 && measured))))
+        return cfgpp_op_attention(q, k, vt, o, B, heads, d, nq, nk, q_tok_pad, k_tok_pad, stream);
+    attn_note(0, 0, 0, 0);
+    CFGPP_REQUIRE(q && k && vt && o, "attention_cross: null pointer");
+    CFGPP_REQUIRE(B > 0 && heads > 0 && nq > 0, "attention_cross: B=%d heads=%d nq=%d", B, heads, nq);
+    CFGPP_REQUIRE(d % 8 == 0, "attention_cross: head dim %d unsupported (multiple of 8)", d);
+    CFGPP_REQUIRE(q_tok_pad % 128 == 0 && q_tok_pad >= nq, "attention_cross: q_tok_pad=%d (nq=%d) must be a multiple of 128", q_tok_pad, nq);
+    CFGPP_REQUIRE(k_tok_pad % 64 == 0 && k_tok_pad >= nk, "attention_cross: k_tok_pad=%d (nk=%d) must be a multiple of 64", k_tok_pad, nk);
+    AttnArgs a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.o = (half_t*)o;
+    a.heads = heads; a.d = d; a.nq = nq; a.nk_valid = nk; a.q_tok_pad = q_tok_pad; a.k_tok_pad = k_tok_pad;
+    a.o_ld = heads * d;
+    a.scale_log2e = (1.0f / sqrtf((float)d)) * 1.4426950408889634f;
+    a.nqb = cdiv(nq, 128);
+    a.stagger = 0;
+    const int d16 = (d + 15) / 16, BH = B * heads;
+    const bool ones = (d % 32) != 0;
+    int xqb = 1;        // the walk of cfgpp_op_attention's cross-attention branch
+    while (xqb < 8 && a.nqb % (xqb * 2) == 0 && (long)BH * (a.nqb / (xqb * 2)) >= 512) xqb *= 2;
+    const int nxb = a.nqb / xqb;
+    constexpr int kMaxSmem = 5 * 2 * 64 * 128;
+    static bool attr_set = false;
+    if (!attr_set) {
+        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_long_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_long_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_long_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+        attr_set = true;
+    }
+    const int smem = ((nk + 63) >> 6) * 2 * 64 * 128;      // <= k_tok_pad * 256 bytes: every tile the DMA reads lies inside the buffers
+    const dim3 xg(BH * nxb);
+    hipStream_t s = (hipStream_t)stream;
+    if (d16 == 3) hipLaunchKernelGGL((xattn64_long_kernel<3, true>), xg, dim3(256), smem, s, a, xqb, nxb);
+    else if (ones) hipLaunchKernelGGL((xattn64_long_kernel<4, true>), xg, dim3(256), smem, s, a, xqb, nxb);
+    else hipLaunchKernelGGL((xattn64_long_kernel<4, false>), xg, dim3(256), smem, s, a, xqb, nxb);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    attn_note(6, d16, ones, xqb);
     return 0;
 }
 

@@ -74,8 +74,19 @@ void cfgpp_attention_set_stagger(int sleeps);
 /* A/B switch: 1 (default) attention with <= 128 keys and head dims padded to 64 (the 77-token cross-attention) runs the
  * resident-K/V single-pass kernel, 0 the flash loop */
 void cfgpp_attention_set_cross(int on);
+/* The UNet's cross-attention op.  Scope of xattn64_long_kernel (last_launch kernel 6: K / V^T resident in LDS, up to five 64-key
+ * tiles, xqb blocks of 128 queries per workgroup, online softmax over the resident tiles): head dims padded to 64 with 129 <= nk <=
+ * 320 keys (a text context of 2 .. 4 chunks of 77 tokens).  With the default switches the part of that scope where it measured
+ * >= 3 % faster than the flash loop takes it: d = 40 / 48 at every key count, d = 56 / 64 at nk <= 192.  Every other shape (the rest of the scope, nk <= 128,
+ * nk > 320, other head dims) is cfgpp_op_attention: same launch, same bits, same record.  Slots [nk, k_tok_pad) may hold anything
+ * finite. */
+int cfgpp_op_attention_cross(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d,
+                             int nq, int nk, int q_tok_pad, int k_tok_pad, void* stream);
+/* A/B switch of cfgpp_op_attention_cross: 1 (default) the resident-K/V kernel for its measured classes, 0 the flash loop
+ * everywhere, 2 the resident-K/V kernel for its whole scope (the kernel's tests, the A/B measurement) */
+void cfgpp_attention_set_cross_long(int mode);
 /* test hook: what the last cfgpp_op_attention call dispatched, a host-side record: out4 = {kernel (0 nothing launched: the call
- * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
+ * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel, 6 xattn64_long_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
  * from the ones row of V^T), xqb (128-query blocks per workgroup of xattn64_kernel, 0 for the flash kernels)} */
 void cfgpp_attention_last_launch(int* out4);
 /* zero key slots [slot0, slot0 + n) of k [BH][tok_pad][dp] and of rows < d of vt [BH][dp][tok_pad] (the ones row stays) */

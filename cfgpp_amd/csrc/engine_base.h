@@ -14,6 +14,7 @@
 
 #include "../../include/cfgpp.h"
 #include "../../include/cfgpp_ip_adapter.h"
+#include "../../include/cfgpp_long_prompt.h"
 #include "cfgpp_debug.h"
 #include "igemm.h"
 

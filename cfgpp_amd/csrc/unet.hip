@@ -27,7 +27,8 @@ struct cfgpp_unet : EngineBase {
     float* d_step_tab = nullptr; int step_tab_cap = 0; float* d_step_cur = nullptr; int* d_step_idx = nullptr;
     hipStream_t cap_stream = nullptr;
     struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; int cond_rows;
-                      int ip_active = 0, ip_n_img = 0; unsigned ip_scale_bits = 0; };      // the adapter state the captured launches baked in
+                      int ip_active = 0, ip_n_img = 0; unsigned ip_scale_bits = 0;         // the adapter state the captured launches baked in
+                      int ctx_tokens = 77; };       // the text context's token count: the captured cross-attention launches bake in nk, the kernel and its LDS size
     struct Graph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<Graph> graphs;              // most recently used last; at most 4 (an invert + edit job alternates between two)
     int tuned_serial = 0;                   // bumps whenever the pins of the current batch change (a graph bakes the tiles it captured)
@@ -51,6 +52,11 @@ struct cfgpp_unet : EngineBase {
     ~cfgpp_unet() { drop_graphs(); if (cap_stream) hipStreamDestroy(cap_stream); for (auto& a : ip_allocs) hipFree(a.first); }
     // context inputs
     const half_t* ctx_ehs = nullptr; int ctx_rows = 0; int ctx_tokens = 77;
+    // longest text context the cross-attention buffers are built for (cfgpp_unet_set_max_tokens, before finalize): 77 * j, j <= 4.
+    // ck / cvt of every block have ck_pad = max(128, round_up(max_tokens, 64)) key slots; a context of fewer tokens leaves slots
+    // [tokens, ck_pad) as an earlier, longer context wrote them - finite values that every attention kernel on the path masks
+    // (P = 0) or never loads, so nothing is cleared.
+    int max_tokens = 77;
     const half_t* ctx_text = nullptr; const float* ctx_tids = nullptr; int ctx_cond_rows = 0;
     bool ctx_set = false;
 
@@ -115,10 +121,12 @@ struct cfgpp_unet : EngineBase {
         for (const IpBlock& b : ip_blocks) {
             const double per_key = 2.0 * (double)b.nheads * b.tok * b.d;
             const std::string desc = "cross_attn heads=" + std::to_string(b.nheads) + " N=" + std::to_string(b.tok) + " d=" + std::to_string(b.d);
-            plan_macs[b.plan_idx] = per_key * (77 + ip_n_img);
-            plan_desc[b.plan_idx] = on ? desc + " ip=" + std::to_string(n_img) : desc;
+            plan_macs[b.plan_idx] = per_key * (ctx_tokens + ip_n_img);
+            plan_desc[b.plan_idx] = on ? desc + " ip=" + std::to_string(n_img) : ctx_tokens != 77 ? desc + " keys=" + std::to_string(ctx_tokens) : desc;
         }
     }
+    // the profiler's tags of the cross-attention ops follow the token count of the current context
+    void retag_cross() { if (plan_macs.size() == plan.size()) ip_set_active(ip_active, ip_n_img, ip_scale); }
     void ip_drop() {
         if (plan_macs.size() == plan.size()) ip_set_active(false, 0, 0.f);
         while (!ip_allocs.empty()) ip_free(ip_allocs.back().first);
@@ -536,7 +544,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         half_t* const HQ = u->hq[lvl]; half_t* const HK = u->hk[lvl]; half_t* const HVT = u->hvt[lvl];
         const int C = x.C, tok = x.H * x.W, d = C / nheads, dp = round_up(d, 32);
         const int q_pad = round_up(tok, 128), k_pad = round_up(tok, 64);
-        const int ck_pad = round_up(u->ctx_tokens, 64);
+        const int ck_pad = std::max(128, round_up(u->max_tokens, 64));
         float* ng = B.f32(p + ".norm.weight"); float* nb = B.f32(p + ".norm.bias");
         half_t* wpi = B.linear(p + ".proj_in.weight"); float* bpi = B.f32(p + ".proj_in.bias");
         half_t* wpo = B.linear(p + ".proj_out.weight"); float* bpo = B.f32(p + ".proj_out.bias");
@@ -608,7 +616,7 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                     if (uu->ip_active)      // IP-Adapter: text + image keys in ONE launch (head dims padded to 64), same launch count
                         return cfgpp_op_attention_ip(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, uu->ip_n_img, uu->ip_scale, q_pad,
                                                      ck_pad, s);
-                    return cfgpp_op_attention(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, q_pad, ck_pad, s);
+                    return cfgpp_op_attention_cross(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, q_pad, ck_pad, s);
                 });
                 u->ip_blocks.back().plan_idx = u->plan.size() - 1;
                 u->ip_macs_per_key += 2.0 * (double)nheads * tok * d;
@@ -770,7 +778,9 @@ int cfgpp_unet_set_context(cfgpp_unet* u, const void* ehs, int rows, int tokens,
                            const void* time_ids, int cond_rows, void* stream) {
     CFGPP_REQUIRE(u && u->finalized, "set_context: context not finalized");
     CFGPP_REQUIRE(ehs && rows > 0 && rows <= u->cfg.max_rows, "set_context: rows=%d (max %d)", rows, u->cfg.max_rows);
-    CFGPP_REQUIRE(tokens == 77, "set_context: tokens=%d (the engine is built for 77 text tokens)", tokens);
+    CFGPP_REQUIRE(tokens >= 77 && tokens % 77 == 0 && tokens <= u->max_tokens,
+                  "set_context: tokens=%d (a multiple of 77 up to max_tokens=%d, which cfgpp_unet_set_max_tokens raises before finalize)", tokens,
+                  u->max_tokens);
     if (u->cfg.addition_embed) {
         CFGPP_REQUIRE(text_embeds && time_ids, "set_context: SDXL needs text_embeds and time_ids");
         CFGPP_REQUIRE(cond_rows == rows || cond_rows == 1, "set_context: cond_rows=%d must be rows (%d) or 1", cond_rows, rows);
@@ -779,6 +789,16 @@ int cfgpp_unet_set_context(cfgpp_unet* u, const void* ehs, int rows, int tokens,
     u->ctx_text = (const half_t*)text_embeds; u->ctx_tids = (const float*)time_ids; u->ctx_cond_rows = cond_rows;
     for (auto& op : u->ctx_plan) { int e = op((hipStream_t)stream, rows); if (e) return e; }
     u->ctx_set = true;
+    u->retag_cross();
+    return 0;
+}
+
+int cfgpp_unet_set_max_tokens(cfgpp_unet* u, int max_tokens) {
+    CFGPP_REQUIRE(u, "set_max_tokens: null engine");
+    CFGPP_REQUIRE(!u->finalized, "set_max_tokens: max_tokens=%d after cfgpp_unet_finalize (the cross-attention buffers are sized there)", max_tokens);
+    CFGPP_REQUIRE(max_tokens == 77 || max_tokens == 154 || max_tokens == 231 || max_tokens == 308,
+                  "set_max_tokens: max_tokens=%d (77, 154, 231 or 308)", max_tokens);
+    u->max_tokens = max_tokens;
     return 0;
 }
 
@@ -812,6 +832,8 @@ static int ip_fail(const char* key, const char* why) { cfgpp_set_error("ip_load:
 int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dtype, const long* shape, int ndim) {
     CFGPP_REQUIRE(u && u->finalized, "ip_load: the engine is not finalized (the adapter attaches to the uploaded UNet)");
     CFGPP_REQUIRE(!u->control, "ip_load: a ControlNet takes no image tokens (diffusers passes it the text context only)");
+    CFGPP_REQUIRE(!key || u->max_tokens == 77, "ip_load: IP-Adapter on an engine with max_tokens=%d (the image slots sit at key 96 of a 128-slot "
+                  "buffer: max_tokens must be 77)", u->max_tokens);
     CFGPP_HIP_CHECK(hipSetDevice(u->device));
     if (!key) {                 // drop the adapter
         CFGPP_HIP_CHECK(hipDeviceSynchronize());        // an earlier forward may still read its K / V^T slots
@@ -1078,11 +1100,12 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
     CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "sample_graph: the image context (IP-Adapter) was set for %d rows, the loop runs %d", u->ip_rows, rows);
     cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
     want.ip_active = u->ip_active ? 1 : 0; want.ip_n_img = u->ip_n_img; std::memcpy(&want.ip_scale_bits, &u->ip_scale, sizeof(float));
+    want.ctx_tokens = u->ctx_tokens;
     auto same = [&](const cfgpp_unet::GraphKey& k) {
         return k.z == want.z && k.z0t == want.z0t && k.eps == want.eps && k.euc == want.euc && k.ec == want.ec && k.z_half == want.z_half &&
                k.z_rows == want.z_rows && k.rows == want.rows && k.tw == want.tw && k.rn == want.rn && k.lam == want.lam && k.n == want.n &&
                k.tuned_serial == u->tuned_serial && k.cond_rows == want.cond_rows && k.ip_active == want.ip_active &&
-               k.ip_n_img == want.ip_n_img && k.ip_scale_bits == want.ip_scale_bits;
+               k.ip_n_img == want.ip_n_img && k.ip_scale_bits == want.ip_scale_bits && k.ctx_tokens == want.ctx_tokens;
     };
     int hit = -1;
     for (size_t i = 0; i < u->graphs.size(); ++i) if (same(u->graphs[i].key)) hit = (int)i;
@@ -1205,7 +1228,8 @@ double cfgpp_unet_flops(cfgpp_unet* u, int rows) {
     // the prefix a CFG call shares is computed once for both halves: counted once when the most recent forward shared it
     const double once = u->ran_shared == 1 ? u->prefix_macs_per_row * (rows / 2) : 0.0;
     const double ip = u->ip_active ? u->ip_macs_per_key * u->ip_n_img : 0.0;      // the image keys, while an adapter is active
-    return 2.0 * ((u->macs_per_row + u->attn_macs_per_row + ip) * rows - once);
+    const double text = u->ip_macs_per_key * (u->ctx_tokens - 77);      // attn_macs_per_row counts 77 text keys per cross-attention
+    return 2.0 * ((u->macs_per_row + u->attn_macs_per_row + text + ip) * rows - once);
 }
 
 void cfgpp_unet_set_share_prefix(int on) { g_share_prefix = on ? 1 : 0; }

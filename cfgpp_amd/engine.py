@@ -170,7 +170,9 @@ class HipUNet:
     """Hand-written HIP UNet behind the C ABI.  One instance per device."""
 
     def __init__(self, cfg: UNetConfig, max_rows: int, sample_hw: Optional[Tuple[int, int]] = None,
-                 device: int = 0):
+                 device: int = 0, max_tokens: int = 77):
+        """``max_tokens``: the longest text context ``set_context`` will take, 77 * j with j <= 4 (include/cfgpp_long_prompt.h:
+        cfgpp_unet_set_max_tokens)"""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise CfgppError("HipUNet needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -186,6 +188,9 @@ class HipUNet:
             raise CfgppError("cfgpp_unet_create failed: " + _lib.last_error())
         self._keep = {}          # tensors the engine holds raw pointers to
         self.finalized = False
+        self.max_tokens = 77
+        if int(max_tokens) != 77:
+            self.set_max_tokens(max_tokens)
         self.latent_channels = cfg.out_channels      # z carries these; an inpaint UNet's other inputs come from image_condition
         self.cond_channels = cfg.in_channels - cfg.out_channels
 
@@ -218,6 +223,12 @@ class HipUNet:
             self.load_tensor(k, v)
         return self
 
+    def set_max_tokens(self, max_tokens: int):
+        """before ``finalize``: size the cross-attention buffers for contexts of up to ``max_tokens`` = 77, 154, 231 or 308 tokens"""
+        check(self.lib.cfgpp_unet_set_max_tokens(self._h, int(max_tokens)), "cfgpp_unet_set_max_tokens")
+        self.max_tokens = int(max_tokens)
+        return self
+
     def finalize(self):
         check(self.lib.cfgpp_unet_finalize(self._h), "cfgpp_unet_finalize")
         self.finalized = True
@@ -226,7 +237,7 @@ class HipUNet:
     # -- conditioning ------------------------------------------------------------
     def set_context(self, ehs: torch.Tensor, text_embeds: Optional[torch.Tensor] = None,
                     time_ids: Optional[torch.Tensor] = None):
-        """ehs [rows,77,D] (uc rows first, then c rows).  SDXL: text_embeds [rows|1,1280], time_ids [rows|1,6]."""
+        """ehs [rows,77 * j,D] with 77 * j <= max_tokens (uc rows first, then c rows).  SDXL: text_embeds [rows|1,1280], time_ids [rows|1,6]."""
         dev = torch.device("cuda", self.device)
         ehs = ehs.to(device=dev, dtype=torch.float16).contiguous()
         rows, tokens = int(ehs.shape[0]), int(ehs.shape[1])

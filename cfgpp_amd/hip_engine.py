@@ -28,7 +28,9 @@ class HipEngine:
     so there is one stream."""
 
     def __init__(self, cfg: UNetConfig, max_batch: int = 1, latent_hw: Optional[Tuple[int, int]] = None,
-                 device=None, weights="synthetic", weight_seed: int = 0):
+                 device=None, weights="synthetic", weight_seed: int = 0, max_tokens: int = 77):
+        """``max_tokens``: the longest text context (77 * j, j <= 4) the UNet - and a ControlNet built by ``build_controlnet`` -
+        accepts; 77 is the default engine, bit for bit"""
         if isinstance(cfg, str):
             cfg = CONFIGS[cfg]
         if not torch.cuda.is_available():
@@ -43,7 +45,8 @@ class HipEngine:
         # device BECOMES the process's current device and stays it - cfgpp_unet_finalize, the lazily allocated K-split
         # workspaces and every launch run against the current device, and none of the C entry points carries a device guard.
         torch.cuda.set_device(self.device)
-        self.unet = E.HipUNet(cfg, max_rows=2 * self.max_batch, sample_hw=latent_hw, device=self.device.index)
+        self.max_tokens = int(max_tokens)
+        self.unet = E.HipUNet(cfg, max_rows=2 * self.max_batch, sample_hw=latent_hw, device=self.device.index, max_tokens=self.max_tokens)
         if weights == "synthetic":
             items = synth_state_dict_iter(cfg, weight_seed)
         elif isinstance(weights, str):
@@ -77,7 +80,7 @@ class HipEngine:
 
     # -- conditioning ------------------------------------------------------------
     def set_context(self, uc: torch.Tensor, c: torch.Tensor, text_embeds=None, time_ids=None):
-        """uc, c: [B or 1, 77, D].  Rows are laid out [uc_1..uc_B, c_1..c_B]
+        """uc, c: [B or 1, 77 * j, D], the same j <= max_tokens / 77 for both.  Rows are laid out [uc_1..uc_B, c_1..c_B]
         (the batched form of torch.cat([uc, c]), latent_diffusion.py:152)."""
         B = max(int(uc.shape[0]), int(c.shape[0]))
         if B > self.max_batch:
@@ -86,6 +89,9 @@ class HipEngine:
             uc = uc.expand(B, -1, -1)
         if c.shape[0] != B:
             c = c.expand(B, -1, -1)
+        if int(uc.shape[1]) != int(c.shape[1]):
+            raise CfgppError(f"set_context: uc has {int(uc.shape[1])} tokens, c {int(c.shape[1])}: pad the shorter prompt with chunks of the "
+                             "empty prompt (cfgpp_amd.prompt)")
         ehs = torch.cat([uc, c], dim=0)
         self.unet.set_context(ehs, text_embeds, time_ids)
         self._ctx = (ehs, text_embeds, time_ids)
@@ -122,7 +128,7 @@ class HipEngine:
         """a ControlNet for this engine's geometry (max_batch, latent size, device): ``spec`` = "synthetic", a diffusers
         ``controlnet/`` folder / safetensors file, or a state dict (controlnet.build_controlnet)"""
         from .controlnet import build_controlnet
-        return build_controlnet(spec, self.cfg, 2 * self.max_batch, (self.H, self.W), self.device.index, seed)
+        return build_controlnet(spec, self.cfg, 2 * self.max_batch, (self.H, self.W), self.device.index, seed, max_tokens=self.max_tokens)
 
     @property
     def control(self):
@@ -133,6 +139,9 @@ class HipEngine:
         """load an IP-Adapter (``ip_adapter.resolve``: "synthetic", a safetensors path, a state dict, a parsed adapter) into the
         UNet, or drop it (None).  UNet weights, tile pins and captured graphs are untouched (include/cfgpp_ip_adapter.h: cfgpp_unet_ip_load)."""
         from .ip_adapter import resolve
+        if spec is not None and self.max_tokens != 77:
+            raise CfgppError(f"ip_adapter=...: IP-Adapter on an engine with max_tokens={self.max_tokens} (max_prompt_chunks > 1) is not "
+                             "supported: the image tokens' key slots sit at key 96 of a 128-slot buffer")
         parsed = resolve(spec, self.cfg)
         if self._ip is not None:     # the drop synchronises the device and clears every block's image slots: only when there is one
             self.unet.ip_load(None)

@@ -103,6 +103,14 @@ class StableDiffusion:
         self.cfg = cfg
         self.latent_hw = tuple(kwargs.get("latent_hw", (cfg.sample_size, cfg.sample_size)))
         self.max_batch = int(kwargs.get("max_batch", 1))
+        # long / weighted prompts (cfgpp_amd/prompt.py): 1 = off (prompts cut at 75 ids, brackets literal); K = 2 .. 4: prompts are
+        # parsed, cut into up to K chunks of 75 ids and the engine is built for text contexts of 77 * K tokens
+        self.max_prompt_chunks = int(kwargs.get("max_prompt_chunks", 1))
+        if not 1 <= self.max_prompt_chunks <= 4:
+            raise ValueError(f"max_prompt_chunks={self.max_prompt_chunks}: 1 (off) .. 4")
+        if self.max_prompt_chunks > 1 and kwargs.get("ip_adapter") is not None:
+            raise ValueError(f"ip_adapter=... together with max_prompt_chunks={self.max_prompt_chunks} is not supported: the IP-Adapter's "
+                             "image tokens sit at key 96 of a 128-slot cross-attention buffer (max_prompt_chunks must be 1)")
 
         # scheduler tables (host)
         self.tables = SchedulerTables(solver_config.num_sampling, self.scheduler_kind)
@@ -118,7 +126,8 @@ class StableDiffusion:
         if engine is None:
             from .hip_engine import HipEngine
             engine = HipEngine(cfg, max_batch=self.max_batch, latent_hw=self.latent_hw, device=device,
-                               weights=kwargs.get("unet_weights", "synthetic"), weight_seed=kwargs.get("weight_seed", 0))
+                               weights=kwargs.get("unet_weights", "synthetic"), weight_seed=kwargs.get("weight_seed", 0),
+                               max_tokens=77 * self.max_prompt_chunks)
         self.engine = engine
         self.unet = engine
         self.work_device = getattr(engine, "device", torch.device("cpu"))
@@ -262,10 +271,34 @@ class StableDiffusion:
 
     @torch.no_grad()
     def get_text_embed(self, null_prompt, prompt):
-        """-> (null_text_embed [1 or B,77,D], text_embed [B,77,D]), fp16."""
+        """-> (null_text_embed [1 or B,77,D], text_embed [B,77,D]), fp16.  With ``max_prompt_chunks`` > 1: [.., 77 * j, D], the same
+        j for both (cfgpp_amd/prompt.py)."""
+        if self.max_prompt_chunks > 1:
+            uc, c = self._long_text_embed(self.text_encoder, [as_list(null_prompt), as_list(prompt)])[0]
+            return uc.to(self.work_device), c.to(self.work_device)
         uc, _ = self.text_encoder(as_list(null_prompt))
         c, _ = self.text_encoder(as_list(prompt))
         return uc.to(self.work_device), c.to(self.work_device)
+
+    @staticmethod
+    def _refuse_long_context_when_sharded(tokens: int):
+        """sharded runs (world size > 1) take one 77-token chunk: every text context - from prompts or from ``prompt_embeds=`` -
+        passes here before it reaches the engine"""
+        if int(tokens) > 77:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise ValueError(f"a text context of {int(tokens)} tokens ({int(tokens) // 77} prompt chunks) in a sharded run (world size > 1) is "
+                                 "not supported: the packed broadcast of the conditioning has the shapes of one 77-token chunk")
+
+    def _long_text_embed(self, encoder, groups, n_chunks=None, clip_skip=None):
+        """``groups`` of prompt lists (uncond, cond, ...) through ``prompt.encode_prompts`` at ONE chunk count, that of the longest
+        prompt of all groups (or ``n_chunks`` if larger) -> ([hidden per group], [pooled per group], j)"""
+        from . import prompt as P
+        K = self.max_prompt_chunks
+        j = max([P.chunks_needed(encoder, g, K) for g in groups] + [int(n_chunks or 1)])
+        self._refuse_long_context_when_sharded(77 * j)
+        enc = [P.encode_prompts(encoder, g, K, n_chunks=j, clip_skip=clip_skip) for g in groups]
+        return [e[0] for e in enc], [e[1] for e in enc], j
 
     def _get_vae(self):
         if self.vae is None:
@@ -311,6 +344,7 @@ class StableDiffusion:
         key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch(), *extra_key)
         changed = getattr(self, "_ctx_key", None) != key
         if changed:
+            self._refuse_long_context_when_sharded(max(int(a.shape[1]), int(b.shape[1])))      # (prompt_embeds= comes this way too)
             self._set_context(a, b, *extra)
             self._ctx_key = key
             self._ctx_keep = (a, b, *extra)
@@ -471,6 +505,9 @@ class StableDiffusion:
         pe = kwargs.get("prompt_embeds")
         if pe is not None:
             return tuple(e.to(self.work_device, torch.float16) for e in pe)
+        if self.max_prompt_chunks > 1:     # every prompt of the call at one chunk count
+            hs = self._long_text_embed(self.text_encoder, [as_list(prompt[k]) for k in range(1 + n_cond)])[0]
+            return tuple(h.to(self.work_device) for h in hs)
         out = []
         uc = None
         for k in range(n_cond):

@@ -62,10 +62,28 @@ class SDXL(StableDiffusion):
         return hs, pooled
 
     @torch.no_grad()
-    def get_text_embed(self, null_prompt_1, prompt_1, null_prompt_2=None, prompt_2=None, clip_skip=None):
+    def get_text_embed(self, null_prompt_1, prompt_1, null_prompt_2=None, prompt_2=None, clip_skip=None, n_chunks=None):
         """-> null_prompt_embeds, prompt_embeds, pool_null_embed, pool_prompt_embed
-        (reference: latent_sdxl.py:95-128; pooled output always from the last encoder used)."""
+        (reference: latent_sdxl.py:95-128; pooled output always from the last encoder used).  With ``max_prompt_chunks`` > 1 both
+        towers cut their prompts alike (one chunk count for both towers and both sides, at least ``n_chunks``), the hidden states
+        are concatenated along features per chunk, and the pooled output is that of chunk 0, unweighted (cfgpp_amd/prompt.py)."""
         enc1, enc2 = self.text_encoder
+        if self.max_prompt_chunks > 1:
+            # the default path below, prompt by prompt, at one chunk count j: (encoder, prompt) of the cond side, then of the uncond side
+            from . import prompt as P
+            K = self.max_prompt_chunks
+            cond = [(enc1, as_list(prompt_1))] + ([(enc2, as_list(prompt_2))] if prompt_2 is not None else [])
+            null = [(enc1, as_list(null_prompt_1))] + ([(enc2, as_list(null_prompt_2))] if null_prompt_2 is not None else [])
+            j = max([P.chunks_needed(e, g, K) for e, g in cond + null] + [int(n_chunks or 1)])
+            pe, ne = [], []
+            for e, g in cond:
+                (h,), (pool,), _ = self._long_text_embed(e, [g], j, clip_skip)
+                pe.append(h)
+            for e, g in null:
+                (h,), (pool_null,), _ = self._long_text_embed(e, [g], j, clip_skip)
+                ne.append(h)
+            dev = self.work_device
+            return (torch.cat(ne, dim=-1).to(dev), torch.cat(pe, dim=-1).to(dev), pool_null.to(dev), pool.to(dev))
         pe1, pool = self._text_embed(prompt_1, enc1, clip_skip)
         pe = [pe1]
         if prompt_2 is not None:
@@ -289,8 +307,14 @@ class EditWardSwapDDIM(BaseDDIM):
         if pe is not None:      # (null, src, tgt, pool_null, pool_src, pool_tgt)
             null_e, src_e, tgt_e, pool_null, pool_src, pool_tgt = (x.to(self.work_device, torch.float16) for x in pe)
         else:
-            null_e, src_e, pool_null, pool_src = self.get_text_embed(prompt1[0], prompt1[1], prompt2[0], prompt2[1], clip_skip)
-            _, tgt_e, _, pool_tgt = self.get_text_embed(prompt1[0], prompt1[2], prompt2[0], prompt2[2], clip_skip)
+            nch = None
+            if self.max_prompt_chunks > 1:      # source and target prompt at one chunk count
+                from . import prompt as P
+                e1, e2 = self.text_encoder
+                nch = max(P.chunks_needed(e1, as_list(p), self.max_prompt_chunks) for p in prompt1[:3])
+                nch = max([nch] + [P.chunks_needed(e2, as_list(p), self.max_prompt_chunks) for p in prompt2[:3] if p is not None])
+            null_e, src_e, pool_null, pool_src = self.get_text_embed(prompt1[0], prompt1[1], prompt2[0], prompt2[1], clip_skip, **({} if nch is None else {"n_chunks": nch}))
+            _, tgt_e, _, pool_tgt = self.get_text_embed(prompt1[0], prompt1[2], prompt2[0], prompt2[2], clip_skip, **({} if nch is None else {"n_chunks": nch}))
         mk = lambda pool: self._cond_kwargs(pool, pool_null, cfg_guidance, original_size, crops_coords_top_left,  # noqa: E731
                                             target_size, negative_original_size, negative_crops_coords_top_left,
                                             negative_target_size, src_e.dtype)

@@ -84,7 +84,13 @@ class HipClipTextTower:
 
     @torch.no_grad()
     def __call__(self, prompts: List[str], clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
-        ids = self.tok(list(prompts)).to(torch.int32)
+        return self.encode_ids(self.tok(list(prompts)), clip_skip)
+
+    @torch.no_grad()
+    def encode_ids(self, ids: torch.Tensor, clip_skip: Optional[int] = None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """ids [n, 77] (``[BOS] + ids + [EOS] + pad``: a prompt, or one 75-id chunk of a long one) -> (hidden, pooled): ``__call__``
+        after the tokenizer, in slices of ``max_batch`` rows"""
+        ids = ids.cpu().to(torch.int32)
         n = ids.shape[0]
         # the pooled row: first EOS of every prompt (transformers: ids == eos_token_id, first hit)
         eos = (ids == int(self.tok.EOS)).to(torch.int32).argmax(dim=-1).to(torch.int32)

@@ -51,6 +51,9 @@ def main(argv=None, solver_kwargs=None) -> None:
     for flag, kind, default in REFERENCE_FLAGS + EXTRA_FLAGS:
         ap.add_argument(f"--{flag}", type=kind, default=default)
     ap.add_argument("--model", default="sd15", choices=("sd15", "sd20", "sdxl", "sdxl_lightning"))
+    ap.add_argument("--max_prompt_chunks", type=int, default=1, choices=(1, 2, 3, 4),
+                    help="2 .. 4: prompts of up to 75 ids per chunk with (emphasis:1.3) / [de-emphasis] / BREAK, the engine built for "
+                         "77 x K text tokens (cfgpp_amd/prompt.py); 1 (default): prompts cut at 75 ids, brackets literal")
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--ip_adapter", default=None, metavar="PATH[:SCALE]",
@@ -85,6 +88,8 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
     ip_kwargs = _ip_kwargs(args, kw)
+    if args.max_prompt_chunks > 1:
+        kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference

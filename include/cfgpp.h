@@ -136,7 +136,8 @@ int cfgpp_unet_missing(cfgpp_unet* u);
 /* Repack all weights into MFMA-friendly device layouts and build the launch plan. */
 int cfgpp_unet_finalize(cfgpp_unet* u);
 
-/* Conditioning for the next forwards: ehs [rows][77][cross_dim] fp16 (uc rows first,
+/* Conditioning for the next forwards: ehs [rows][tokens][cross_dim] fp16, tokens = 77 (or 77 * j, see
+ * include/cfgpp_long_prompt.h) (uc rows first,
  * then c rows: the `torch.cat([uc, c])` of latent_diffusion.py:152); SDXL:
  * text_embeds [cond_rows][1280] fp16, time_ids [cond_rows][6] fp32, cond_rows = rows or 1
  * (1 = broadcast, the lambda==1.0 Lightning case of latent_sdxl.py:249-252).
