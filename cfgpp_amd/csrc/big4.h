@@ -11,6 +11,7 @@ inline void big4_tile(int cfg, int* BM, int* BN) {
 // span < 4 GiB; pixel indices and row pitches < 2^24 for the 24-bit multiply), and the 320-wide tile has no GEGLU pairs.
 inline bool big4_supports(int cfg, const IGemmArgs& a, bool staged_epi) {
     if (cfg < 24 || cfg > 26 || !staged_epi || a.K < 64) return false;
+    if (a.amode == 4) return false;                     // the 2x2 phase form is not instantiated for this family
     const long rows = a.amode == 0 ? (long)a.M : a.amode == 2 ? (long)(a.M / a.rows_per_batch) * (2 * a.H + 2) * (2 * a.W + 2)
                                                 : (long)(a.M / a.rows_per_batch) * (a.H + 2) * (a.W + 2);      // (amode 3 reads a smaller map)
     const long cmax = a.C0 > a.C1 ? a.C0 : a.C1;

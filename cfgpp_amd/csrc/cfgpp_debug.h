@@ -161,11 +161,33 @@ int cfgpp_op_f16_to_f32_rows(const void* in, float* out, int rows, int cols, int
  * a0/a1: activation sources (C0/C1 channels), amode 0 linear rows, 1 halo-padded NHWC,
  * 2 padded stride-2, 3 padded nearest-2x upsample; w [N][taps*(C0+C1)] fp16 with K order channel-block major,
  * tap minor: k = (cb*taps + tap)*64 + c, cb = 64-channel block of the concatenated input;
- * epi 0 store (+bias +temb +resid), 1 GEGLU (packed weights).  omode/rmode: 0 linear, 1 padded. */
+ * epi 0 store (+bias +temb +resid), 1 GEGLU (packed weights).  omode/rmode: 0 linear, 1 padded.
+ * amode 4 ("2x2 phase"): the upsample + conv3x3 of amode 3 as four 2x2 convolutions over the source map, one per output parity:
+ * taps = 4, one source, H x W still the (even) OUTPUT size and M = rows * H * W, w = the folded weights of cfgpp_op_fold_upsample
+ * ([4 phases][N][4 * C0]), epi 0 into a padded output (omode 1), no temb / resid, N % 8 == 0.  Rows are computed phase-outermost
+ * (phase = 2 py + px, n, i, j): tap (a, b) reads padded source pixel (n, i + py + a, j + px + b), the row lands on padded output
+ * pixel (n, 2i + py + 1, 2j + px + 1).  Tiles: every family but the one-wave-per-SIMD configs 24 - 26 / 28 and the 64 x 160 wave
+ * tiles on 32-deep K-tiles (20 / 27), which report "did not run"; never K-split. */
 int cfgpp_op_igemm(const void* a0, const void* a1, int C0, int C1, int taps, int amode, int H, int W,
                    const void* w, int M, int N, const float* bias, const float* temb, int temb_ld,
                    const void* resid, int rmode, int rld, void* out, int omode, int old_, int epi,
                    void* stream);
+/* w9: a conv3x3 weight in the repacked layout [O][I/64][9][64] fp16 (I % 64 == 0) -> w4 [4][O][I/64][4][64]: per output parity
+ * (py, px) the 2x2 kernel whose taps are sums of 1, 2, 2 or 4 of the 3x3 taps (1-D: p = 0: a0 <- {t0}, a1 <- {t1, t2}; p = 1: a0 <-
+ * {t0, t1}, a1 <- {t2}), summed in fp32 (t ascending, then s ascending) and rounded once */
+int cfgpp_op_fold_upsample(const void* w9, void* w4, int O, int I, void* stream);
+/* nearest-2x upsample + conv3x3 (+bias) of a padded Hs x Ws x C source into a padded 2Hs x 2Ws x N output, dispatched as the
+ * engines' plan builder does: the 2x2 phase form (amode 4, reads w4) when the switch below is on and the source map is at least
+ * 8 x 8, else the 9-tap amode-3 launch (reads w9) */
+int cfgpp_op_upsample_conv3x3(const void* src, int C, int Hs, int Ws, const void* w9, const void* w4, int rows, int N,
+                              const float* bias, void* out, void* stream);
+/* 1 (default): plans built from now on run their upsampler convolutions in the 2x2 phase form; 0: the 9-tap form (A/B).  Read
+ * when a plan is built (finalize), not per forward. */
+void cfgpp_igemm_set_upsample_phase(int on);
+/* test hooks: the A-operand mode of the last implicit-GEMM launch; 1 when that launch ran the tile config it was asked for (forced
+ * or pinned), 0 when the config does not support the launch and another tile ran */
+int cfgpp_igemm_last_amode(void);
+int cfgpp_igemm_last_config_ran(void);
 /* QKV / KV projection with head-major scatter (EPI_HEADS) */
 int cfgpp_op_igemm_heads(const void* a, int K, const void* w, int M, int N, const float* bias, int rows_per_batch,
                          void* hq, void* hk, void* hvt, int part0, int part_width, int head_dim, int heads,

@@ -202,6 +202,24 @@ struct EngineBase {
             t.gst = (float*)dmalloc((size_t)max_rows * (H * W / 32) * C * 2 * sizeof(float), false);
         return t;
     }
+    // Upsampler convolutions in the 2x2 phase form (IGemmArgs::amode 4) read a FOLDED copy of their weight: [4 phases][O][I/64][4][64],
+    // 16/9 of the 3x3 weight's size, made on the device from the registered SLOT_CONV3 parameter - which stays the LoRA merge
+    // target and what a read-back returns.  Folded when the plan is built and again after every write to that parameter (refold).
+    struct FoldSite { const half_t* w9; half_t* w4; long O, I; };
+    std::vector<FoldSite> folds;
+    half_t* fold_site(const half_t* w9, long O, long I) {
+        half_t* w4 = (half_t*)dmalloc((size_t)16 * O * I * sizeof(half_t), false);
+        if (!w4) return nullptr;
+        if (igemm_fold_upsample_launch(w9, w4, O, I, nullptr) != 0 || hipStreamSynchronize(nullptr) != hipSuccess) return nullptr;
+        folds.push_back({w9, w4, O, I});
+        return w4;
+    }
+    // the 3x3 weight at w9 was rewritten on stream s (adapter merge / restore): its folded copy follows, in stream order
+    int refold(const half_t* w9, hipStream_t s) {
+        for (const FoldSite& f : folds)
+            if (f.w9 == w9) { const int e = igemm_fold_upsample_launch(f.w9, f.w4, f.O, f.I, s); if (e) return e; }
+        return 0;
+    }
     void rel(const Tensor& t) { if (t.p) pool[std::make_tuple(t.H, t.W, t.C)].push_back(std::make_pair(t.p, t.gst)); }
     ~EngineBase() { for (void* p : allocs) hipFree(p); }
 };
@@ -339,6 +357,11 @@ IGemmArgs base_args(EngineBase* u = nullptr) {
     return a;
 }
 
+// nearest-2x upsample + conv3x3 from an Hs x Ws source map: does the plan emit the 2x2 phase form?  (The switch is read HERE, when a
+// plan is built.  Maps under 8 x 8 keep the 9-tap launch: a phase of a small batch is then less than one M-tile.  A supporting
+// tile family exists for every shape the builder produces - one source, channels in multiples of 64, N % 8 == 0.)
+inline bool upsample_phase_form(int Hs, int Ws, int N) { return igemm_upsample_phase_enabled() && Hs >= 8 && Ws >= 8 && N % 8 == 0; }
+
 struct Plan {
     EngineBase* u;
     Builder* B;
@@ -355,10 +378,21 @@ struct Plan {
         a.out = dst.p; a.omode = 1; a.old = dst.C; a.epi = EPI_STORE;
         a.gstat = dst.gst; a.stat_flag = dst.gst ? dst.gst_ok : nullptr;      // the consumer GroupNorm takes its statistics from this epilogue
         const int HW = dst.H * dst.W;
+        std::string issued;
+        if (amode == 3 && !resid && !temb && upsample_phase_form(src.H, src.W, dst.C)) {
+            // four 2x2 convs over the source map, one per output parity: K = 4 * C instead of 9 * C, same M, N and output
+            half_t* w4 = u->fold_site(w, dst.C, src.C);
+            if (!w4) { B->ok = false; B->err = "folded upsampler weight: out of device memory"; }
+            else {
+                a.amode = amode = 4; a.taps = 4; a.w = w4; a.K = 4 * src.C;
+                issued = " as 4x2x2 K=" + std::to_string(a.K);
+            }
+        }
+        // (the plan counts the operation's ALGORITHMIC MACs - 9 taps - whichever form is issued)
         u->macs_per_row += (double)HW * dst.C * 9.0 * src.C;
         int* hint = u->new_hint(ops == &u->plan);
         ops->push_back([a, HW, hint](hipStream_t s, int rows) mutable { IGemmArgs b = a; b.M = rows * HW; b.cfg_hint = *hint; return igemm_launch(b, s); });
-        if (ops == &u->plan) u->tag(0, (double)HW * dst.C * 9.0 * src.C, "conv3x3 amode=" + std::to_string(amode) + " HW=" + std::to_string(HW) + " N=" + std::to_string(dst.C) + " K=" + std::to_string(9 * src.C) + (resid ? " +res" : "") + (temb ? " +temb" : ""));
+        if (ops == &u->plan) u->tag(0, (double)HW * dst.C * 9.0 * src.C, "conv3x3 amode=" + std::to_string(amode) + " HW=" + std::to_string(HW) + " N=" + std::to_string(dst.C) + " K=" + std::to_string(9 * src.C) + issued + (resid ? " +res" : "") + (temb ? " +temb" : ""));
     }
     // 1x1 conv over (src0 || src1) padded -> padded
     void conv1x1(const Tensor& s0, const Tensor* s1, const Tensor& dst, const half_t* w, const float* bias) {

@@ -13,8 +13,12 @@ struct IGemmArgs {
     const half_t* a0;
     const half_t* a1;
     int C0, C1;        // channels of each source, multiples of 64 (C1 may be 0)
-    int taps;          // 1 (linear / 1x1) or 9 (3x3, pad 1)
-    int amode;         // 0 linear rows, 1 padded NHWC, 2 padded stride-2, 3 padded nearest-2x upsample
+    int taps;          // 1 (linear / 1x1), 9 (3x3, pad 1) or 4 (amode 4: the 2x2 phase convs of an upsampled 3x3)
+    int amode;         // 0 linear rows, 1 padded NHWC, 2 padded stride-2, 3 padded nearest-2x upsample, 4 "2x2 phase": the same
+                       // upsample + conv3x3 as four 2x2 convs over the SOURCE map, one per output parity (py, px), K = 4 * C0.
+                       // Rows are phase-outermost, m = (phase = 2 py + px, n, i, j) over the source map; tap (a, b) reads padded
+                       // source pixel (n, i + py + a, j + px + b); the row goes to padded output pixel (n, 2i + py + 1, 2j + px + 1);
+                       // w = [4 phases][N][K] folded weights (cfgpp_op_fold_upsample), one source, EPI_STORE, omode 1, no residual
     int H, W;          // OUTPUT spatial size (amode >= 1): rows m enumerate (n, y, x)
     int ashift;        // amode 2 only: 0 = pad 1 (UNet downsample), 1 = pad (0,1,0,1) (VAE encoder downsample)
     // ---- B operand: weights [N][K] fp16, K = taps*(C0+C1).  K order is CHANNEL-BLOCK major, tap minor:
@@ -69,6 +73,8 @@ struct IGemmArgs {
     // time then share activation row-blocks AND weight slabs in its 4-MiB L2.  Chosen by the launcher from a count of the bytes
     // each round of resident workgroups pulls into the L2 (walk_plan); results do not depend on it.
     int walk_bn, walk_per, walk_tmb, walk_tnb;
+    int ph_tiles;             // amode 4 (filled by the launcher, which hands the kernel ONE phase's view: M, H, W, rows_per_batch of the
+                              // source map, omode 2): M-tiles per phase - M-tile t is tile t % ph_tiles of phase t / ph_tiles
     int split;                // >= 2: K-split every tile this many ways (igemm_launch's big-tile rule / diagnostics); 0: launcher's rule
     // ---- diagnostics (cfgpp_igemm_timeline): per-workgroup time stamps of ONE chosen launch, null otherwise ----
     int par_nb;               // time-embedding rows (batches) a tile stages in LDS (set by the launcher: covers every batch a tile's rows touch)
@@ -80,4 +86,6 @@ struct IGemmArgs {
 int igemm_launch(const IGemmArgs& a, hipStream_t stream);
 int igemm_autotune_enabled();
 int igemm_last_hint_applied();     // did the last igemm_launch run the tile its cfg_hint named?
+int igemm_upsample_phase_enabled();             // cfgpp_igemm_set_upsample_phase
+int igemm_fold_upsample_launch(const half_t* w9, half_t* w4, long O, long I, hipStream_t stream);
 unsigned igemm_tune_mask();

@@ -52,6 +52,17 @@ __device__ __forceinline__ int padded_pix(int m, int HW, int W, int H) {
     const int y = qdiv(p, W), x = p - y * W;
     return (b * (H + 2) + y + 1) * (W + 2) + x + 1;
 }
+// amode 4 (2x2 phase form of upsample + conv3x3): row m of ONE phase enumerates the SOURCE map (n, i, j) of H x W pixels; phase
+// (py, px) = (phase >> 1, phase & 1) owns padded output pixel (n, 2i + py + 1, 2j + px + 1) of the 2H x 2W map
+__device__ __forceinline__ int phase_pix(int m, int HW, int W, int H, int phase) {
+    const int b = qdiv(m, HW), p = m - b * HW;
+    const int i = qdiv(p, W), j = p - i * W;
+    return (b * (2 * H + 2) + 2 * i + (phase >> 1) + 1) * (2 * W + 2) + 2 * j + (phase & 1) + 1;
+}
+// ... and its taps: tap (a, b) reads padded source pixel (n, i + py + a, j + px + b) = phase_src_pix + a * (W + 2) + b
+__device__ __forceinline__ int phase_src_pix(int m, int HW, int W, int H, int phase) {
+    return padded_pix(m, HW, W, H) + ((phase >> 1) - 1) * (W + 2) + (phase & 1) - 1;
+}
 
 
 // workgroup index (XCD-contiguous numbering) -> tile.  Everything here is wave-uniform: the quotients go back to SGPRs
@@ -71,6 +82,17 @@ __device__ __forceinline__ void tile_of(const IGemmArgs& p, int wg, int& tile_m,
         tile_m = p.n_major ? wr : wq; tile_n = p.n_major ? wq : wr;
     }
 }
+// amode 4: M-tile index -> (phase, tile inside the phase).  A tile never mixes phases, so the weight base is wave-uniform.
+template <int AMODE>
+__device__ __forceinline__ int phase_of(const IGemmArgs& p, int& tile_m) {
+    if constexpr (AMODE == 4) {
+        const int ph = qdiv_u(tile_m, p.ph_tiles);
+        tile_m = __builtin_amdgcn_readfirstlane(tile_m - ph * p.ph_tiles);
+        return ph;
+    } else {
+        return 0;
+    }
+}
 
 // ---- epilogue parameters in LDS -----------------------------------------------------------------------------------------
 // The per-column parameters of an epilogue (bias, per-batch time embedding, LayerNorm column sums) used to be read from
@@ -87,6 +109,7 @@ __host__ __device__ constexpr int par_bytes(int BN, int nb = PAR_NB) { return pa
 struct Par {
     const char* lds;     // null: read the parameters from global memory (register-staged kernels, the K-split reduce kernel)
     int n0, b0, bnp;     // first column / first batch of the tile, padded segment length (floats)
+    int phase = 0;       // amode 4: the tile's phase
 };
 // issue the DMA pieces (64 floats each) of the tile's parameter segments; NW = waves of the workgroup
 template <int BN, int NW>
@@ -145,7 +168,7 @@ __device__ __forceinline__ void acc_row_pin(f32x16 (&row)[NT]) {
     }
 }
 // Shared epilogue.  lane: m = mw0 + i*32 + (lane&31);  n = nw0 + j*32 + 8*g + 4*(lane>>5) + {0..3}, g = reg>>2
-template <int MT, int NT, bool L>
+template <int MT, int NT, bool L, int AMODE = 0>
 __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)[MT][NT], int mw0, int nw0, int lane, const Par& par) {
     const int frow = lane & 31, fhi = lane >> 5;
     const int HW = p.rows_per_batch;
@@ -156,7 +179,9 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)
         const int b = (HW > 0) ? qdiv(m, HW) : 0;
         const int tok = m - b * HW;
         long orow = m, rrow = m;
-        if (p.omode == 1 || p.rmode == 1) {
+        if constexpr (AMODE == 4) {
+            orow = phase_pix(m, HW, p.W, p.H, par.phase);
+        } else if (p.omode == 1 || p.rmode == 1) {
             const long pp = padded_pix(m, HW, p.W, p.H);
             if (p.omode == 1) orow = pp;
             if (p.rmode == 1) rrow = pp;
@@ -259,9 +284,18 @@ __device__ __forceinline__ void igemm_epilogue(const IGemmArgs& p, f32x16 (&acc)
 // order: (mean, M2) per column, written as one float4 per pair.  The arithmetic per (block, column) is the same whatever tile
 // config staged the block, so the statistics - like the outputs - do not depend on tile tuning.
 template <int WTN, int PITCH>
-__device__ __forceinline__ void gstat_block(const IGemmArgs& p, const char* stg, int m_blk0, int nw0, int lane) {
+__device__ __forceinline__ void gstat_block(const IGemmArgs& p, const char* stg, int m_blk0, int nw0, int lane, int phase = -1) {
     if (m_blk0 >= p.M) return;
-    float* dst = p.gstat + ((long)(m_blk0 >> 5) * p.N + nw0) * 2;
+    int slot = m_blk0 >> 5;
+    if (phase >= 0) {
+        // amode 4: the blocks of sample n and phase ph fill slots [n * nb + ph * bps, .. + bps) of the sample's nb = 4 * bps (the
+        // launcher writes statistics only when H * W % 32 == 0: a block then lies inside one sample)
+        // (wave-uniform: m_blk0 is the wave's block)
+        const int bps = p.rows_per_batch >> 5;
+        slot = __builtin_amdgcn_readfirstlane(slot);
+        slot += (3 * qdiv_u(slot, bps) + phase) * bps;
+    }
+    float* dst = p.gstat + ((long)slot * p.N + nw0) * 2;
     // (rolled loops on purpose: unrolled, the 31 LDS reads of a pass are hoisted into 31 more live registers, which the tiles that
     //  sit at their register budget - 64 x 160 waves at 243 of 256, the four-waves-per-SIMD 256 x 128 tile at 126 of 128 - spill)
 #pragma unroll 1
@@ -287,7 +321,7 @@ __device__ __forceinline__ void gstat_block(const IGemmArgs& p, const char* stg,
 // row segments (WTN*2 bytes contiguous, 16 B per lane): coalesced residual loads and output stores.
 // bias / time-embedding are added in fp32 before the (single) rounding to fp16; the residual is added to
 // the fp16 value, which is exactly the reference's `conv(...)` (fp16) `+ residual` (fp16) order.
-template <int MT, int NT, bool L, bool PIN = false>
+template <int MT, int NT, bool L, bool PIN = false, int AMODE = 0>
 __device__ __forceinline__ void igemm_epilogue_staged(const IGemmArgs& p, f32x16 (&acc)[MT][NT], int mw0, int nw0, int lane,
                                                       char* stg /* wave-private, 32 * (NT*64 + 16) bytes */, const Par& par) {
     constexpr int WTN = NT * 32;
@@ -309,7 +343,9 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IGemmArgs& p, f32x16
         const int b = (HW > 0) ? qdiv(mc, HW) : 0;
         // this lane's row: output / residual pixel index (shared with the other lanes by shuffle below)
         int opix = mc, rpix = mc;
-        if (p.omode == 1 || p.rmode == 1) {
+        if constexpr (AMODE == 4) {
+            opix = phase_pix(mc, HW, p.W, p.H, par.phase);          // (no residual in this mode: igemm_launch)
+        } else if (p.omode == 1 || p.rmode == 1) {
             const int pp = padded_pix(mc, HW, p.W, p.H);
             if (p.omode == 1) opix = pp;
             if (p.rmode == 1) rpix = pp;
@@ -365,7 +401,7 @@ __device__ __forceinline__ void igemm_epilogue_staged(const IGemmArgs& p, f32x16
             }
             if (c < 32 * CPR && mm < p.M && n < p.N) *reinterpret_cast<half8_t*>(p.out + (long)op * p.old + n) = v;
         }
-        if (p.gstat) gstat_block<WTN, PITCH>(p, stg, mw0 + i * 32, nw0, lane);
+        if (p.gstat) gstat_block<WTN, PITCH>(p, stg, mw0 + i * 32, nw0, lane, AMODE == 4 ? par.phase : -1);
     }
 }
 

@@ -84,6 +84,7 @@ igemm_kernel(const IGemmArgs p) {
     // (one division by a launcher-provided divisor: a two-sided branch here cost the 256 x 320 kernel 30 VGPRs -> spills)
     int tile_m, tile_n;
     tile_of(p, wg, tile_m, tile_n);                        // (K-split tails never take the blocked walk: walk_bn = 0)
+    const int phase = phase_of<AMODE>(p, tile_m);         // amode 4: the tile's phase; tile_m = tile inside the phase
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -103,6 +104,8 @@ igemm_kernel(const IGemmArgs p) {
         else if constexpr (AMODE == 2) {
             const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
             a_pix[j] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
+        } else if constexpr (AMODE == 4) {
+            a_pix[j] = phase_src_pix(m, HW, p.W, p.H, phase);
         } else {
             const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
             a_pix[j] = (b << 22) | (y << 11) | x;      // unpacked per tap
@@ -116,7 +119,7 @@ igemm_kernel(const IGemmArgs p) {
     for (int j = 0; j < B_CH; ++j) {
         int n = n0 + lrow + j * RSTEP;
         n = n < p.N ? n : p.N - 1;
-        b_ptr[j] = p.w + (long)n * p.K + schunk * 8;
+        b_ptr[j] = p.w + ((long)phase * p.N + n) * p.K + schunk * 8;
     }
     // LDS store offsets (swizzled), identical for both operands
     int st_off[(A_CH > B_CH ? A_CH : B_CH)];
@@ -133,7 +136,8 @@ igemm_kernel(const IGemmArgs p) {
 
     auto load_tile = [&](int kt) {
         int tap = 0, cc = kt << 6;
-        if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
+        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
+        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
         const bool s0 = cc < p.C0;
         const half_t* src = s0 ? p.a0 : p.a1;
         const int cs = s0 ? cc : cc - p.C0, Cs = s0 ? p.C0 : p.C1;
@@ -142,6 +146,7 @@ igemm_kernel(const IGemmArgs p) {
         int dpix = 0;
         if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
         else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
+        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
 #pragma unroll
         for (int j = 0; j < A_CH; ++j) {
             int pix;
@@ -161,7 +166,8 @@ igemm_kernel(const IGemmArgs p) {
     const int wave_row0 = __builtin_amdgcn_readfirstlane(wid) * 8;
     auto dma_tile = [&](int kt, int stage) {
         int tap = 0, cc = kt << 6;
-        if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
+        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
+        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
         const bool s0 = cc < p.C0;
         const half_t* src = s0 ? p.a0 : p.a1;
         const int cs = s0 ? cc : cc - p.C0, Cs = s0 ? p.C0 : p.C1;
@@ -170,6 +176,7 @@ igemm_kernel(const IGemmArgs p) {
         int dpix = 0;
         if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
         else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
+        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
         char* As = smem + stage * STAGE_BYTES;
         char* Bs = As + BM * 128;
 #pragma unroll
@@ -254,13 +261,15 @@ igemm_kernel(const IGemmArgs p) {
             char* Bsn = Asn + BM * 128;
             if constexpr (DMA) {
                 int tap = 0, cc = ktn << 6;
-                if (p.taps == 9) { const int cb = ktn / 9; tap = ktn - cb * 9; cc = cb << 6; }
+                if constexpr (AMODE == 4) { tap = ktn & 3; cc = (ktn >> 2) << 6; }
+                else if (p.taps == 9) { const int cb = ktn / 9; tap = ktn - cb * 9; cc = cb << 6; }
                 const bool s0 = cc < p.C0;
                 src = s0 ? p.a0 : p.a1;
                 cs = s0 ? cc : cc - p.C0; Cs = s0 ? p.C0 : p.C1;
                 if (p.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
                 if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
                 else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
+        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
             }
             auto piece = [&](int q) {
                 if (q < A_CH) {
@@ -448,11 +457,11 @@ igemm_kernel(const IGemmArgs p) {
         return;
     }
     Par par;
-    par.lds = GLDS ? smem + PAR_OFF : nullptr; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN);
+    par.lds = GLDS ? smem + PAR_OFF : nullptr; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN); par.phase = phase;
     constexpr bool STAGED_FITS = WM * WN * 32 * (WTN * 2 + 16) <= NST * STAGE_BYTES;      // (256 x 320 with 32 x 320 waves: 164 KB, no)
     if (STAGED_FITS && p.epi == EPI_STORE && (p.N & 7) == 0 && p.staged_epi) {
         // the k-loop ended with a barrier: every wave is done with the tile stages, LDS is free
-        igemm_epilogue_staged<MT, NT, GLDS>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
+        igemm_epilogue_staged<MT, NT, GLDS, false, AMODE>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
         tl_end(p.tl);
         return;
     }
@@ -471,7 +480,7 @@ igemm_kernel(const IGemmArgs p) {
         tl_end(p.tl);
         return;
     }
-    igemm_epilogue<MT, NT, GLDS>(p, acc, mw0, nw0, lane, par);
+    igemm_epilogue<MT, NT, GLDS, AMODE>(p, acc, mw0, nw0, lane, par);
     tl_end(p.tl);
 }
 
@@ -556,6 +565,7 @@ tile32_kernel(const IGemmArgs p) {
     }
     int tile_m, tile_n;
     tile_of(p, wg, tile_m, tile_n);
+    const int phase = phase_of<AMODE>(p, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -582,6 +592,8 @@ tile32_kernel(const IGemmArgs p) {
             else if constexpr (AMODE == 2) {
                 const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
                 a_pix[q] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
+            } else if constexpr (AMODE == 4) {
+                a_pix[q] = phase_src_pix(m, HW, p.W, p.H, phase);
             } else {
                 const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
                 a_pix[q] = (b << 22) | (y << 11) | x;
@@ -590,7 +602,7 @@ tile32_kernel(const IGemmArgs p) {
         } else {
             int n = n0 + (g - A_P) * 16 + prow;
             n = n < p.N ? n : p.N - 1;
-            b_ptr[q] = p.w + (long)n * p.K + schunk * 8;
+            b_ptr[q] = p.w + ((long)phase * p.N + n) * p.K + schunk * 8;
             dst[q] = BM * 64 + (g - A_P) * 16 * 64;
         }
     }
@@ -599,7 +611,8 @@ tile32_kernel(const IGemmArgs p) {
         Gather g;
         const int k64 = kt >> 1;
         int tap = 0, cc = k64 << 6;
-        if (p.taps == 9) { const int cb = k64 / 9; tap = k64 - cb * 9; cc = cb << 6; }
+        if constexpr (AMODE == 4) { tap = k64 & 3; cc = (k64 >> 2) << 6; }
+        else if (p.taps == 9) { const int cb = k64 / 9; tap = k64 - cb * 9; cc = cb << 6; }
         const bool s0 = cc < p.C0;
         g.src = s0 ? p.a0 : p.a1;
         g.cs = (s0 ? cc : cc - p.C0) + ((kt & 1) << 5); g.Cs = s0 ? p.C0 : p.C1;
@@ -608,6 +621,7 @@ tile32_kernel(const IGemmArgs p) {
         g.dpix = 0;
         if constexpr (AMODE == 1) g.dpix = g.dy * (p.W + 2) + g.dx;
         else if constexpr (AMODE == 2) g.dpix = g.dy * (2 * p.W + 2) + g.dx;
+        else if constexpr (AMODE == 4) g.dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
         return g;
     };
     auto piece = [&](int q, int kt, int stage, const Gather& g) {      // q compile-time after unrolling
@@ -748,10 +762,10 @@ tile32_kernel(const IGemmArgs p) {
 
     const int mw0 = m0 + wm * WTM, nw0 = n0 + wn * WTN;
     Par par;
-    par.lds = smem + PAR_OFF; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN);
+    par.lds = smem + PAR_OFF; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN); par.phase = phase;
     constexpr bool STAGED_FITS = NW * 32 * (WTN * 2 + 16) <= NST * STAGE_BYTES;
     if (STAGED_FITS && p.epi == EPI_STORE && (p.N & 7) == 0 && p.staged_epi) {
-        igemm_epilogue_staged<MT, NT, true>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
+        igemm_epilogue_staged<MT, NT, true, false, AMODE>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
         tl_end(p.tl);
         return;
     }
@@ -769,7 +783,7 @@ tile32_kernel(const IGemmArgs p) {
         tl_end(p.tl);
         return;
     }
-    igemm_epilogue<MT, NT, true>(p, acc, mw0, nw0, lane, par);
+    igemm_epilogue<MT, NT, true, AMODE>(p, acc, mw0, nw0, lane, par);
     tl_end(p.tl);
 }
 
@@ -790,7 +804,7 @@ tile32_kernel(const IGemmArgs p) {
 //     (cfgpp_igemm_set_mf16_heads); whole tiles only (no K-split).
 // The 16 x 16 x 32 MFMA sums k in a different order than the 32 x 32 x 16 one, so this tile is NOT a tuner candidate (the
 // tuner's choices must not change results): it is used by rule (igemm_launch; cfgpp_igemm_set_mf16) or forced (configs 18 / 19).
-template <bool L = true>
+template <bool L = true, int AMODE = 0>
 __device__ __forceinline__ void igemm_epilogue_staged16(const IGemmArgs& p, f32x4 (&acc)[2][5], int mw0, int nw0, int lane,
                                                         char* stg /* wave-private, 32 * 176 bytes */, const Par& par) {
     constexpr int WTN = 80, PITCH = WTN * 2 + 16, CPR = WTN / 8, NQ = (32 * CPR + 63) / 64;
@@ -801,7 +815,9 @@ __device__ __forceinline__ void igemm_epilogue_staged16(const IGemmArgs& p, f32x
     const int mr = mw0 + frow;
     const int mrc = mr < p.M ? mr : p.M - 1;
     int opix = mrc, rpix = mrc;
-    if (p.omode == 1 || p.rmode == 1) {
+    if constexpr (AMODE == 4) {
+        opix = phase_pix(mrc, HW, p.W, p.H, par.phase);
+    } else if (p.omode == 1 || p.rmode == 1) {
         const int pp = padded_pix(mrc, HW, p.W, p.H);
         if (p.omode == 1) opix = pp;
         if (p.rmode == 1) rpix = pp;
@@ -866,7 +882,7 @@ __device__ __forceinline__ void igemm_epilogue_staged16(const IGemmArgs& p, f32x
         }
         if (c < 32 * CPR && mm < p.M && n < p.N) *reinterpret_cast<half8_t*>(p.out + (long)op * p.old + n) = v;
     }
-    if (p.gstat) gstat_block<WTN, PITCH>(p, stg, mw0, nw0, lane);
+    if (p.gstat) gstat_block<WTN, PITCH>(p, stg, mw0, nw0, lane, AMODE == 4 ? par.phase : -1);
 }
 
 // EPI_HEADS for the 16 x 16 accumulator layout: the wave's 32-token x 80-column slab goes through LDS as five
@@ -960,6 +976,7 @@ igemm16_kernel(const IGemmArgs p) {
     }
     int tile_m, tile_n;
     tile_of(p, wg, tile_m, tile_n);
+    const int phase = phase_of<AMODE>(p, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -980,6 +997,8 @@ igemm16_kernel(const IGemmArgs p) {
         else if constexpr (AMODE == 2) {
             const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
             a_pix[j] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
+        } else if constexpr (AMODE == 4) {
+            a_pix[j] = phase_src_pix(m, HW, p.W, p.H, phase);
         } else {
             const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
             a_pix[j] = (b << 22) | (y << 11) | x;
@@ -991,7 +1010,7 @@ igemm16_kernel(const IGemmArgs p) {
     for (int j = 0; j < 3; ++j) {
         int n = n0 + lrow + j * RSTEP;
         n = n < p.N ? n : p.N - 1;
-        b_ptr[j] = p.w + (long)n * p.K + schunk * 8;
+        b_ptr[j] = p.w + ((long)phase * p.N + n) * p.K + schunk * 8;
     }
     const int wave_row0 = wid * 8;
 
@@ -999,7 +1018,8 @@ igemm16_kernel(const IGemmArgs p) {
     auto gather_of = [&](int kt) {
         Gather g;
         int tap = 0, cc = kt << 6;
-        if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
+        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
+        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
         const bool s0 = cc < p.C0;
         g.src = s0 ? p.a0 : p.a1;
         g.cs = s0 ? cc : cc - p.C0; g.Cs = s0 ? p.C0 : p.C1;
@@ -1008,6 +1028,7 @@ igemm16_kernel(const IGemmArgs p) {
         g.dpix = 0;
         if constexpr (AMODE == 1) g.dpix = g.dy * (p.W + 2) + g.dx;
         else if constexpr (AMODE == 2) g.dpix = g.dy * (2 * p.W + 2) + g.dx;
+        else if constexpr (AMODE == 4) g.dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
         return g;
     };
     // piece q of K-tile kt into `stage`: q = 0, 1 activation passes; 2, 3 weight passes; 4 the half weight pass (b3 waves)
@@ -1151,9 +1172,9 @@ igemm16_kernel(const IGemmArgs p) {
 #undef CFGPP_WAIT_TILES
 
     Par par;
-    par.lds = smem + PAR_OFF; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN);
+    par.lds = smem + PAR_OFF; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN); par.phase = phase;
     if (p.epi == EPI_HEADS) igemm_epilogue_heads_staged16(p, acc, m0 + wm * 32, n0 + wn * 80, lane, smem + wid * (5 * 1536), par);
-    else igemm_epilogue_staged16(p, acc, m0 + wm * 32, n0 + wn * 80, lane, smem + wid * (32 * 176), par);
+    else igemm_epilogue_staged16<true, AMODE>(p, acc, m0 + wm * 32, n0 + wn * 80, lane, smem + wid * (32 * 176), par);
     tl_end(p.tl);
 }
 
@@ -1184,6 +1205,12 @@ static float* ws_for(hipStream_t stream) {
 }
 static int g_staged_epi = 1;
 static int g_last_hint_applied = 1;                 // see igemm_last_hint_applied()
+// 2x2 phase form of the upsampler convolutions (amode 4): read when a plan is built (engine_base.h), default on
+static int g_upsample_phase = 1;
+extern "C" void cfgpp_igemm_set_upsample_phase(int on) { g_upsample_phase = on ? 1 : 0; }
+static int g_last_amode = -1;          // test hooks: A-operand mode of the last igemm_launch / did it run the tile that was asked for
+extern "C" int cfgpp_igemm_last_amode(void) { return g_last_amode; }
+extern "C" int cfgpp_igemm_last_config_ran(void) { return g_last_hint_applied; }
 extern "C" void cfgpp_igemm_set_staged_epilogue(int on) { g_staged_epi = on ? 1 : 0; }
 static int g_big_tiles = 1;
 extern "C" void cfgpp_igemm_set_big_tiles(int on) { g_big_tiles = on ? 1 : 0; }
@@ -1210,6 +1237,19 @@ static int par_slots(const IGemmArgs& a, int BM) {
 // depend on the walk; the tuner's pinned 1-D walks are left alone.
 static int g_walk_blocked = 1;
 extern "C" void cfgpp_igemm_set_blocked_walk(int on) { g_walk_blocked = on ? 1 : 0; }
+// unique activation bytes per output row, relative to Cin * 2: a stride-2 conv reads a 4x larger map, the fused upsample a 4x
+// smaller one.  amode 4 arrives here in its per-phase view (M = rows of ONE phase = pixels of the source map, phase_view): each
+// phase reads the source map once, so a phase row costs one source row
+static double a_traffic(const IGemmArgs& a) { return a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0; }
+// unique activation bytes of the whole launch (amode 4 in its per-phase view: four phases, each reads the source map once)
+static double a_bytes_of(const IGemmArgs& a) { return 2.0 * a.M * (a.amode == 4 ? 4.0 : 1.0) * (a.C0 + a.C1) * a_traffic(a); }
+// amode 4: the kernel sees ONE phase - M, H, W, rows_per_batch of the SOURCE map, output row map 2 (phase_pix) - and the grid
+// covers four of them.  Returns the M-tiles of the launch.
+static int phase_view(IGemmArgs& a, int BM) {
+    a.H >>= 1; a.W >>= 1; a.rows_per_batch = a.H * a.W; a.M >>= 2; a.omode = 2;
+    a.ph_tiles = cdiv(a.M, BM);
+    return 4 * a.ph_tiles;
+}
 static void walk_plan(IGemmArgs& a, int BM, int BN, int ntm, int ntn, int smem) {
     a.walk_bn = 0; a.walk_per = 0; a.walk_tmb = 0; a.walk_tnb = 0;
     const int T = ntm * ntn;
@@ -1218,7 +1258,7 @@ static void walk_plan(IGemmArgs& a, int BM, int BN, int ntm, int ntn, int smem) 
     int wpc = smem > 0 ? (160 * 1024) / smem : 1;
     wpc = wpc < 1 ? 1 : wpc > 4 ? 4 : wpc;
     const int R = 32 * wpc;                                   // tiles an XCD runs at a time
-    const double a_row = 2.0 * BM * (a.C0 + a.C1) * (a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0);
+    const double a_row = 2.0 * BM * (a.C0 + a.C1) * a_traffic(a);
     const double w_col = 2.0 * BN * a.K;
     // bytes XCD 0 pulls in, round by round: distinct tile rows x a_row + distinct tile columns x w_col
     auto cost = [&](auto tile_at) {
@@ -1270,7 +1310,9 @@ extern "C" void cfgpp_igemm_walk_plan_probe(int M, int N, int K, int BM, int BN,
 // Decided HERE, per launch, and reported to the caller through *stat_flag (host memory): a consumer must not trust a buffer the
 // launch did not fill.
 static void stats_decide(IGemmArgs& a, bool staged_store) {
-    const bool on = a.gstat != nullptr && staged_store && a.epi == EPI_STORE && (a.N & 7) == 0 && (a.M & 31) == 0 && a.ksplit <= 1 && a.n_main > 0;
+    // (amode 4, per-phase view: a 32-row block must lie inside one sample of one phase)
+    const bool on = a.gstat != nullptr && staged_store && a.epi == EPI_STORE && (a.N & 7) == 0 && (a.M & 31) == 0 && a.ksplit <= 1 && a.n_main > 0 &&
+                    (a.amode != 4 || (a.rows_per_batch & 31) == 0);
     if (!on) a.gstat = nullptr;
     if (a.stat_flag) *a.stat_flag = on ? 1 : 0;
 }
@@ -1283,6 +1325,7 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     constexpr int blocks_per_cu = (160 * 1024) / smem_std < 8 ? (160 * 1024) / smem_std : 8;
     constexpr int slots = 256 * blocks_per_cu;       // resident workgroups on 256 CUs
     IGemmArgs a = a_in;
+    const int ntm = AMODE == 4 ? phase_view(a, BM) : cdiv(a.M, BM);
     a.par_nb = par_slots(a, BM);
     const int smem = NST * (BM + BN) * 128 + (GLDS ? par_bytes(BN, a.par_nb > PAR_NB ? a.par_nb : PAR_NB) : 0);
     if (smem > 160 * 1024) {
@@ -1298,11 +1341,11 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_smem = smem;
     }
-    const int T = cdiv(a.M, BM) * cdiv(a.N, BN);
+    const int T = ntm * cdiv(a.N, BN);
     const int KT = a.K >> 6;
     a.n_main = T; a.ksplit = 1; a.ws = nullptr; a.staged_epi = g_staged_epi;
     {   // weight bytes vs unique activation bytes (a 3x3 conv re-reads each pixel through L2: its A operand is M x Cin)
-        const double w_bytes = 2.0 * a.N * a.K, a_bytes = 2.0 * a.M * (a.C0 + a.C1) * (a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0);
+        const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
         a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && cdiv(a.N, BN) >= 8)) ? 1 : 0;
         if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
     }
@@ -1312,7 +1355,8 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     // that T*S fills the resident slots once or twice.
     {
         int S = 0;
-        if (a_in.split >= 2 && a.epi == EPI_STORE) S = a_in.split < KT ? a_in.split : KT;
+        if (AMODE == 4) S = 0;      // (the reduce kernel knows no phases: the 2x2 phase form runs whole tiles)
+        else if (a_in.split >= 2 && a.epi == EPI_STORE) S = a_in.split < KT ? a_in.split : KT;
         else if (g_tail_split && a_in.allow_split && (WTM == 64 && WTN == 64) && a.epi == EPI_STORE && T * 2 <= slots && KT >= 32) {
             // at most ONE round of resident workgroups: rounding up (80 tiles x 7 slices = 560 workgroups on 512 slots) left
             // a second round of 48 stragglers as long as the first (g_tail_split == 2 keeps that for A/B)
@@ -1328,8 +1372,8 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     const int n_tail = T - a.n_main;
     stats_decide(a, WM * WN * 32 * (WTN * 2 + 16) <= NST * (BM + BN) * 128 && a.staged_epi && n_tail == 0);
     if (n_tail > 0) a.n_major = 0;                     // K-split tiles keep the M-major numbering the reduce kernel uses
-    a.walk_div = a.n_major ? cdiv(a.M, BM) : cdiv(a.N, BN);
-    walk_plan(a, BM, BN, cdiv(a.M, BM), cdiv(a.N, BN), smem);
+    a.walk_div = a.n_major ? ntm : cdiv(a.N, BN);
+    walk_plan(a, BM, BN, ntm, cdiv(a.N, BN), smem);
     a.tl = tl_take(WM * 100 + WN * 10 + (GLDS ? 1 : 0), a.n_main + n_tail * a.ksplit, NTHR, BM, BN, NST, a);
     hipLaunchKernelGGL(kern, dim3(a.n_main + n_tail * a.ksplit), dim3(NTHR), smem, stream, a);
     if (n_tail > 0)
@@ -1345,6 +1389,7 @@ int launch_cfg(const IGemmArgs& a, hipStream_t stream) {
         case 1: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 1, NST>(a, stream);
         case 2: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 2, NST>(a, stream);
         case 3: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 3, NST>(a, stream);
+        case 4: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 4, NST>(a, stream);
         default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
     }
 }
@@ -1356,6 +1401,7 @@ int launch_tile32_amode(const IGemmArgs& a_in, hipStream_t stream) {
     constexpr int WGS = WPE * 4 / (WM * WN);              // workgroups that are meant to share a CU
     static_assert((NST * (BM + BN) * 64 + par_bytes(BN)) * WGS <= 160 * 1024, "the workgroups that are meant to share a CU do not fit its LDS");
     IGemmArgs a = a_in;
+    const int ntm = AMODE == 4 ? phase_view(a, BM) : cdiv(a.M, BM);
     a.par_nb = par_slots(a, BM);
     const int nb = a.temb ? (a.par_nb > PAR_NB ? a.par_nb : PAR_NB) : 0;
     const int smem = NST * (BM + BN) * 64 + par_bytes(BN, nb);
@@ -1372,9 +1418,9 @@ int launch_tile32_amode(const IGemmArgs& a_in, hipStream_t stream) {
         CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_smem = smem;
     }
-    const int ntm = cdiv(a.M, BM), ntn = cdiv(a.N, BN);
+    const int ntn = cdiv(a.N, BN);
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = g_staged_epi;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = 2.0 * a.M * (a.C0 + a.C1) * (a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0);
+    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
     a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
     if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
     a.walk_div = a.n_major ? ntm : ntn;
@@ -1392,6 +1438,10 @@ int launch_tile32(const IGemmArgs& a, hipStream_t stream) {
         case 1: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 1>(a, stream);
         case 2: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 2>(a, stream);
         case 3: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 3>(a, stream);
+        // (the 64 x 160 wave tiles - configs 20 / 27 - sit at 256 VGPRs and would spill with the phase maps: the 2x2 phase form is not
+        //  instantiated for them; the 256 x 320 tile of igemm_kernel runs instead and the candidate reports that it did not run)
+        case 4: if constexpr (WTN == 160) { g_last_hint_applied = 0; return launch_cfg_amode<4, 2, 64, 160, true, 4, 2>(a, stream); }
+                else return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 4>(a, stream);
         default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
     }
 }
@@ -1413,6 +1463,7 @@ static bool mf16_supports(const IGemmArgs& a) {
 template <int AMODE, int NST>
 int launch_mf16_amode(const IGemmArgs& a_in, hipStream_t stream) {
     IGemmArgs a = a_in;
+    const int ntm = AMODE == 4 ? phase_view(a, 128) : cdiv(a.M, 128);
     a.par_nb = par_slots(a, 128);
     const int smem = NST * (128 + 160) * 128 + par_bytes(160, a.par_nb > PAR_NB ? a.par_nb : PAR_NB);
     if (smem > 160 * 1024) { g_last_hint_applied = 0; return launch_cfg_amode<4, 1, 32, 160, true, AMODE, 2>(a_in, stream); }   // (feature maps under 8 x 8: see launch_cfg_amode)
@@ -1422,9 +1473,9 @@ int launch_mf16_amode(const IGemmArgs& a_in, hipStream_t stream) {
         CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         attr_smem = smem;
     }
-    const int ntm = cdiv(a.M, 128), ntn = a.N / 160;
+    const int ntn = a.N / 160;
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = 1;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = 2.0 * a.M * (a.C0 + a.C1) * (a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0);
+    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
     a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
     if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
     a.walk_div = a.n_major ? ntm : ntn;
@@ -1442,6 +1493,7 @@ int launch_mf16(const IGemmArgs& a, hipStream_t stream) {
         case 1: return launch_mf16_amode<1, NST>(a, stream);
         case 2: return launch_mf16_amode<2, NST>(a, stream);
         case 3: return launch_mf16_amode<3, NST>(a, stream);
+        case 4: return launch_mf16_amode<4, NST>(a, stream);
         default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
     }
 }
@@ -1460,7 +1512,7 @@ static int launch_big4(int cfg, const IGemmArgs& a_in, hipStream_t stream) {
     const int smem = big4_smem(cfg, a);
     const int ntm = cdiv(a.M, BM), ntn = cdiv(a.N, BN);
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = 1;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = 2.0 * a.M * (a.C0 + a.C1) * (a.amode == 2 ? 4.0 : a.amode == 3 ? 0.25 : 1.0);
+    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
     a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
     if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
     a.walk_div = a.n_major ? ntm : ntn;
@@ -1542,10 +1594,13 @@ static int launch_config(int cfg, const IGemmArgs& a, hipStream_t stream) {
         case 18: return mf16_supports(a) ? launch_mf16<3>(a, stream) : launch_cfg<4, 1, 32, 160, true>(a, stream);
         case 19: return mf16_supports(a) ? launch_mf16<4>(a, stream) : launch_cfg<4, 1, 32, 160, true>(a, stream);
         // one wave per SIMD (big4_kernel.hip); launches they do not admit (generic epilogues, > 4 GiB operands) take the 128 x 128 tile
-        case 24: case 25: case 26: return big4_ok(cfg, a) ? launch_big4(cfg, a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
+        // (no 2x2 phase form, amode 4, in that family: the candidate did not run)
+        case 24: case 25: case 26: if (a.amode == 4) g_last_hint_applied = 0;
+                 return big4_ok(cfg, a) ? launch_big4(cfg, a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
         // the 256 x 256 one-wave-per-SIMD tile as a persistent kernel with the next output tile's first K-tile prefetched under the
         // epilogue (big4p_kernel.hip): token-major linears only
-        case 28: return big4p_ok(a) ? launch_big4p(a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
+        case 28: if (a.amode == 4) g_last_hint_applied = 0;
+                 return big4p_ok(a) ? launch_big4p(a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
         default: cfgpp_set_error("igemm: bad config %d", cfg); return -2;
     }
 }
@@ -1592,7 +1647,7 @@ unsigned igemm_tune_mask() { return g_tune_mask; }
 // while this still has the value it had when the engine was built (cfgpp_amd/tune_cache.py)
 extern "C" unsigned cfgpp_igemm_tuner_state(void) {
     return g_tune_mask ^ ((unsigned)g_big_tiles << 1) ^ ((unsigned)g_tail_split << 3) ^ ((unsigned)(g_n_major + 1) << 6) ^ ((unsigned)g_walk_blocked << 9) ^
-           ((unsigned)g_staged_epi << 10) ^ ((unsigned)g_force_cfg << 12) ^ ((unsigned)g_staging << 20);
+           ((unsigned)g_staged_epi << 10) ^ ((unsigned)(g_upsample_phase ^ 1) << 11) ^ ((unsigned)g_force_cfg << 12) ^ ((unsigned)g_staging << 20);
 }
 
 // Arms the timeline: the `target`-th igemm_launch call from now on (0-based) records 16 x uint64 per workgroup (slots: see
@@ -1607,20 +1662,27 @@ extern "C" void cfgpp_igemm_timeline_info(int* out12) { for (int i = 0; i < 12; 
 // launch (rule-based K-split / 16x16x32 tile, GEGLU on a 320-wide tile, ...) and the heuristic tile ran instead: the tuner must
 // not record a time for a candidate that did not run.
 int igemm_last_hint_applied() { return g_last_hint_applied; }
+int igemm_upsample_phase_enabled() { return g_upsample_phase; }
 
 int igemm_launch(const IGemmArgs& a_in, hipStream_t stream) {
     IGemmArgs a = a_in;
+    g_last_amode = a.amode;
     g_last_hint_applied = (a_in.cfg_hint & 63) == 0 ? 1 : 0;
     a.allow_split = 1;
     a.tl = nullptr;
     if (g_tl) { if (g_tl_count == g_tl_target) a.tl = g_tl; ++g_tl_count; }
     const int Cin = a.C0 + a.C1;
     CFGPP_REQUIRE(a.C0 > 0 && a.C0 % 64 == 0 && a.C1 % 64 == 0, "igemm: C0=%d C1=%d must be multiples of 64", a.C0, a.C1);
-    CFGPP_REQUIRE(a.taps == 1 || a.taps == 9, "igemm: taps=%d", a.taps);
+    CFGPP_REQUIRE(a.amode >= 0 && a.amode <= 4, "igemm: bad amode %d", a.amode);
+    CFGPP_REQUIRE(a.amode == 4 ? a.taps == 4 : (a.taps == 1 || a.taps == 9), "igemm: taps=%d (amode %d)", a.taps, a.amode);
     CFGPP_REQUIRE(a.K == a.taps * Cin, "igemm: K=%d != taps*Cin=%d", a.K, a.taps * Cin);
     CFGPP_REQUIRE(a.N % 4 == 0 && a.M > 0 && a.N > 0, "igemm: M=%d N=%d (N must be a multiple of 4)", a.M, a.N);
     CFGPP_REQUIRE(a.amode == 0 || (a.H > 0 && a.W > 0 && a.rows_per_batch == a.H * a.W), "igemm: spatial args");
     CFGPP_REQUIRE(a.amode != 3 || (a.H < 2048 && a.W < 2048 && (a.M / a.rows_per_batch) < 512), "igemm: upsample range");
+    // amode 4: one source, even output size, whole samples, plain store into the padded output, nothing that is mapped by output row
+    CFGPP_REQUIRE(a.amode != 4 || (a.C1 == 0 && a.H % 2 == 0 && a.W % 2 == 0 && a.M % a.rows_per_batch == 0 && a.epi == EPI_STORE && a.omode == 1 &&
+                                   a.resid == nullptr && a.temb == nullptr && a.N % 8 == 0 && (long)(a.M / a.rows_per_batch) * (a.H + 2) * (a.W + 2) < (1L << 31)),
+                  "igemm: 2x2 phase form (amode 4) needs one source, even H x W, M a multiple of H * W, a plain store (N %% 8 == 0) into a padded output, no residual / time embedding");
     CFGPP_REQUIRE(a.epi != EPI_GEGLU || a.N % 64 == 0, "igemm: GEGLU needs N %% 64 == 0");
     CFGPP_REQUIRE(a.epi != EPI_HEADS || (a.head_dim % 4 == 0 && a.part_width % 4 == 0), "igemm: heads args");
     CFGPP_REQUIRE(a.rows_per_batch <= 0 || a.M / a.rows_per_batch < (1 << 20), "igemm: %d rows in batches of %d (batch index must stay below 2^20)", a.M, a.rows_per_batch);
@@ -1677,11 +1739,11 @@ int igemm_launch(const IGemmArgs& a_in, hipStream_t stream) {
         const long t128 = (long)cdiv(a.M, 128) * cdiv(a.N, 128);
         // (must say "splits" exactly when launch_cfg_amode will: T * 2 <= resident slots of that tile)
         const long t_rule = cfg == 14 ? (long)cdiv(a.M, 256) * cdiv(a.N, 128) : t128;
-        const bool rule_splits = (cfg == 1 || cfg == 12 || cfg == 14) && g_tail_split && a.epi == EPI_STORE && KT >= 32 && t_rule * 2 <= (cfg == 1 ? 512 : 256);
+        const bool rule_splits = a.amode != 4 && (cfg == 1 || cfg == 12 || cfg == 14) && g_tail_split && a.epi == EPI_STORE && KT >= 32 && t_rule * 2 <= (cfg == 1 ? 512 : 256);
         const int h = a.cfg_hint & 63;
         const bool valid = (h == 1 || h == 4 || h == 6 || h == 12 || h == 14 || (h == 10 && a.epi == EPI_GEGLU) ||
                             ((h == 5 || h == 7 || h == 8 || h == 9 || h == 11) && a.epi != EPI_GEGLU) ||
-                            h == 13 || h == 15 || h == 16 || h == 17 || (h == 20 && a.epi != EPI_GEGLU) || (h == 27 && a.epi == EPI_STORE) || ((h >= 24 && h <= 26) && big4_ok(h, a)) || (h == 28 && big4p_ok(a))) && (g_big_tiles || h == 1);
+                            h == 13 || h == 15 || h == 16 || h == 17 || (h == 20 && a.epi != EPI_GEGLU) || (h == 27 && a.epi == EPI_STORE) || ((h >= 24 && h <= 26) && a.amode != 4 && big4_ok(h, a)) || (h == 28 && big4p_ok(a))) && (g_big_tiles || h == 1);
         if (!rule_splits && valid) { cfg = h; a.allow_split = 0; g_last_hint_applied = 1; }
     }
     a.walk_hint = (g_force_cfg == 0 && g_staging != 0) ? (a.cfg_hint >> 6) & 3 : 0;      // tuner-pinned tile walk (0 = by operand bytes)

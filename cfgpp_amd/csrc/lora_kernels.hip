@@ -95,7 +95,48 @@ __global__ __launch_bounds__(256) void lora_merge_kernel(const half_t* __restric
     }
 }
 
+// Folded weights of the 2x2 phase form of `nearest-2x upsample -> conv3x3` (IGemmArgs::amode 4).  Output pixel y = 2i + p reads,
+// through tap t (dy = t - 1), source row i + floor((p + t - 1) / 2); with the 2-tap index a reading source row i + p - 1 + a:
+// p = 0: a = 0 <- {t = 0}, a = 1 <- {t = 1, 2};  p = 1: a = 0 <- {t = 0, 1}, a = 1 <- {t = 2}.  2-D is the outer product, so a folded
+// weight is the sum of 1, 2, 2 or 4 taps: summed in fp32 in a fixed order (t ascending, then s ascending), rounded ONCE to fp16.
+//   w9 [O][I/64][9][64]  (SLOT_CONV3)   ->   w4 [4 phases = 2 py + px][O][I/64][4 taps = 2 a + b][64]
+// One thread per 8 consecutive channels of one folded tap.
+__global__ __launch_bounds__(256) void fold_upsample_kernel(const half_t* __restrict__ w9, half_t* __restrict__ w4, long O, long CB) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;          // ((((phase * O + o) * CB + cb) * 4 + tap) * 8 + c8
+    if (idx >= 4 * O * CB * 32) return;
+    const int c8 = (int)(idx & 7), tap = (int)((idx >> 3) & 3);
+    const long r = idx >> 5, cb = r % CB, po = r / CB, o = po % O;
+    const int phase = (int)(po / O);
+    const int py = phase >> 1, px = phase & 1, a = tap >> 1, b = tap & 1;
+    // taps [lo, hi] of one axis: (p, a) = (0, 0) -> 0..0, (0, 1) -> 1..2, (1, 0) -> 0..1, (1, 1) -> 2..2
+    const int t0 = a == 0 ? 0 : 1 + py, t1 = a == 0 ? py : 2;
+    const int s0 = b == 0 ? 0 : 1 + px, s1 = b == 0 ? px : 2;
+    const half_t* src = w9 + ((o * CB + cb) * 9) * 64 + c8 * 8;
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+    for (int t = t0; t <= t1; ++t)
+        for (int s = s0; s <= s1; ++s) {
+            const half8_t v = *reinterpret_cast<const half8_t*>(src + (t * 3 + s) * 64);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) acc[k] += (float)v[k];
+        }
+    half8_t out;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) out[k] = (half_t)acc[k];
+    *reinterpret_cast<half8_t*>(w4 + idx * 8) = out;
+}
+
 }  // namespace
+
+// engine-internal launcher (engine_base.h; cfgpp_op_fold_upsample): w9 = a conv3x3 weight in the repacked layout, w4 = 16 * O * I halfs
+int igemm_fold_upsample_launch(const half_t* w9, half_t* w4, long O, long I, hipStream_t s) {
+    CFGPP_REQUIRE(w9 && w4 && O > 0 && I > 0 && I % 64 == 0 && O * I < (1L << 34), "fold_upsample: bad args (O=%ld, I=%ld: a multiple of 64)", O, I);
+    const long n = 4 * O * (I / 64) * 32;
+    hipLaunchKernelGGL(fold_upsample_kernel, dim3((unsigned)cdiv(n, 256L)), dim3(256), 0, s, w9, w4, O, I / 64);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
 
 // engine-internal launcher (unet.hip).  kind: 0 plain, 1 conv3x3 repack (I % 64 == 0), 2 GEGLU interleave (O % 64 == 0)
 int lora_merge_launch(const half_t* base, half_t* dst, const float* up, const float* down, int rank, int kind, long O, long I,

@@ -1266,7 +1266,10 @@ int cfgpp_unet_lora(cfgpp_unet* u, const char* key, const float* up, const float
     hipStream_t s = (hipStream_t)stream;
     const size_t bytes = (size_t)w->O * w->K() * sizeof(half_t);
     if (rank == 0) {                        // restore; a parameter never merged into still is its base
-        if (w->base) CFGPP_HIP_CHECK(hipMemcpyAsync(w->rows(), w->base, bytes, hipMemcpyDeviceToDevice, s));
+        if (w->base) {
+            CFGPP_HIP_CHECK(hipMemcpyAsync(w->rows(), w->base, bytes, hipMemcpyDeviceToDevice, s));
+            return u->refold(w->rows(), s);     // (an upsampler conv in the 2x2 phase form reads a folded copy)
+        }
         return 0;
     }
     if (!w->base) {                         // first merge into this parameter: keep what finalize uploaded (until destroy)
@@ -1277,8 +1280,8 @@ int cfgpp_unet_lora(cfgpp_unet* u, const char* key, const float* up, const float
     }
     const int kind = w->kind == SLOT_MEMBER ? SLOT_PLAIN : w->kind;
     int e = lora_merge_launch(w->base, w->rows(), up, down, rank, kind, w->O, w->I, w->taps, s);
-    if (e) { const std::string m = cfgpp_last_error(); cfgpp_set_error("lora: %s: %s", key, m.c_str()); }
-    return e;
+    if (e) { const std::string m = cfgpp_last_error(); cfgpp_set_error("lora: %s: %s", key, m.c_str()); return e; }
+    return u->refold(w->rows(), s);             // (an upsampler conv in the 2x2 phase form reads a folded copy)
 }
 
 // test / debugging hook (cfgpp_debug.h): the current weight of `key`, un-repacked to checkpoint order ([O][I][kh][kw] / [O][I])
@@ -1322,6 +1325,23 @@ int cfgpp_op_igemm(const void* a0, const void* a1, int C0, int C1, int taps, int
     a.w = (const half_t*)w; a.M = M; a.N = N; a.K = taps * (C0 + C1); a.bias = bias; a.temb = temb; a.temb_ld = temb_ld;
     a.rows_per_batch = H * W; a.resid = (const half_t*)resid; a.rmode = rmode; a.rld = rld;
     a.out = (half_t*)out; a.omode = omode; a.old = old_; a.epi = epi;
+    a.gstat = g_op_gstat; a.stat_flag = &g_op_gstat_flag; g_op_gstat_flag = 0;
+    return igemm_launch(a, (hipStream_t)stream);
+}
+
+int cfgpp_op_fold_upsample(const void* w9, void* w4, int O, int I, void* stream) {
+    return igemm_fold_upsample_launch((const half_t*)w9, (half_t*)w4, O, I, (hipStream_t)stream);
+}
+
+// nearest-2x upsample + conv3x3 as the plan builder emits it (Plan::conv3x3): the 2x2 phase form when upsample_phase_form says
+// so, else the 9-tap launch
+int cfgpp_op_upsample_conv3x3(const void* src, int C, int Hs, int Ws, const void* w9, const void* w4, int rows, int N,
+                              const float* bias, void* out, void* stream) {
+    IGemmArgs a = base_args();
+    const bool ph = w4 != nullptr && upsample_phase_form(Hs, Ws, N);
+    a.a0 = (const half_t*)src; a.C0 = C; a.taps = ph ? 4 : 9; a.amode = ph ? 4 : 3; a.H = 2 * Hs; a.W = 2 * Ws;
+    a.w = (const half_t*)(ph ? w4 : w9); a.M = rows * a.H * a.W; a.N = N; a.K = a.taps * C; a.bias = bias;
+    a.rows_per_batch = a.H * a.W; a.out = (half_t*)out; a.omode = 1; a.old = N; a.epi = EPI_STORE;
     a.gstat = g_op_gstat; a.stat_flag = &g_op_gstat_flag; g_op_gstat_flag = 0;
     return igemm_launch(a, (hipStream_t)stream);
 }
