@@ -130,6 +130,9 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_f16_to_f32_rows": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_op_igemm": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _P]),
     "cfgpp_op_igemm_heads": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_op_igemm_ex": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _P, _I, _P, _I, _I, _P, _I, _I, _I, _I, _F, _I, _P]),
+    "cfgpp_op_igemm_heads_ex": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "cfgpp_igemm_last_launch": (None, [C.POINTER(C.c_int)]),
     "cfgpp_op_fold_upsample": (_I, [_P, _P, _I, _I, _P]),
     "cfgpp_op_upsample_conv3x3": (_I, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P]),
     "cfgpp_igemm_set_upsample_phase": (None, [_I]),

@@ -172,6 +172,12 @@ int cfgpp_op_igemm(const void* a0, const void* a1, int C0, int C1, int taps, int
                    const void* w, int M, int N, const float* bias, const float* temb, int temb_ld,
                    const void* resid, int rmode, int rld, void* out, int omode, int old_, int epi,
                    void* stream);
+/* cfgpp_op_igemm plus ashift (amode 2: 0 = pad 1, 1 = pad (0,1,0,1)), out_scale (multiplies the accumulator before the bias) and
+ * cfg_hint (the tuner's pin: bits 0-5 tile config, bits 6-7 tile walk) */
+int cfgpp_op_igemm_ex(const void* a0, const void* a1, int C0, int C1, int taps, int amode, int H, int W,
+                      const void* w, int M, int N, const float* bias, const float* temb, int temb_ld,
+                      const void* resid, int rmode, int rld, void* out, int omode, int old_, int epi,
+                      int ashift, float out_scale, int cfg_hint, void* stream);
 /* w9: a conv3x3 weight in the repacked layout [O][I/64][9][64] fp16 (I % 64 == 0) -> w4 [4][O][I/64][4][64]: per output parity
  * (py, px) the 2x2 kernel whose taps are sums of 1, 2, 2 or 4 of the 3x3 taps (1-D: p = 0: a0 <- {t0}, a1 <- {t1, t2}; p = 1: a0 <-
  * {t0, t1}, a1 <- {t2}), summed in fp32 (t ascending, then s ascending) and rounded once */
@@ -185,13 +191,24 @@ int cfgpp_op_upsample_conv3x3(const void* src, int C, int Hs, int Ws, const void
  * when a plan is built (finalize), not per forward. */
 void cfgpp_igemm_set_upsample_phase(int on);
 /* test hooks: the A-operand mode of the last implicit-GEMM launch; 1 when that launch ran the tile config it was asked for (forced
- * or pinned), 0 when the config does not support the launch and another tile ran */
+ * or pinned), 0 when the config does not support the launch and another tile ran (cfgpp_igemm_last_launch says which).  A forced
+ * config whose wave tiles have no GEGLU epilogue (3, 5, 7 - 9, 11 and their register-staged forms) refuses a GEGLU launch. */
 int cfgpp_igemm_last_amode(void);
 int cfgpp_igemm_last_config_ran(void);
 /* QKV / KV projection with head-major scatter (EPI_HEADS) */
 int cfgpp_op_igemm_heads(const void* a, int K, const void* w, int M, int N, const float* bias, int rows_per_batch,
                          void* hq, void* hk, void* hvt, int part0, int part_width, int head_dim, int heads,
                          int q_tok_pad, int tok_pad, void* stream);
+/* the same with vt_linear: 1 = V^T columns in natural key order (the VAE), 0 = the attention kernel's permuted order */
+int cfgpp_op_igemm_heads_ex(const void* a, int K, const void* w, int M, int N, const float* bias, int rows_per_batch,
+                            void* hq, void* hk, void* hvt, int part0, int part_width, int head_dim, int heads,
+                            int q_tok_pad, int tok_pad, int vt_linear, void* stream);
+/* test hook: what the last implicit-GEMM launch ISSUED, after every fallback of the launcher - a host-side record, zeroed at the
+ * entry of every launch (a refused call reports zeros).  out16 = {kernel family (1 igemm_kernel, 2 tile32_kernel, 3 igemm16_kernel,
+ * 4 big4_kernel, 5 big4p_kernel), BM, BN, LDS stages, AMODE as instantiated, operand staging (1 LDS-DMA, 0 registers), grid,
+ * ksplit (1 = whole tiles), n_major as finally set, walk_bn (0 = 1-D walk), par_nb, dynamic LDS bytes, producer statistics written,
+ * epilogue variant (0 generic, 1 staged store, 2 staged GEGLU, 3 staged heads), waves along M, waves along N} */
+void cfgpp_igemm_last_launch(int* out16);
 /* 0 = heuristic, 1 = 128x128, 2 = 256x64, 3 = 64x64, 4 = 256x256, 5 = 256x320, 6 = 256x128, 7 = 128x160, 8 = 128x320,
  * 10 = 256x320 (waves along M); 9 / 11 = 128x160 on a 3- / 4-stage LDS ring, 12 = 128x128 and 14 = 256x128 on 3 stages;
  * 15 / 16 / 17 = 256x128 (8 waves) / 128x128 / 256x64 (4 waves) on 32-deep K-tiles and three stages, 2 - 3 workgroups per CU;

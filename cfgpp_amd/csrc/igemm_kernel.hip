@@ -1317,6 +1317,37 @@ static void stats_decide(IGemmArgs& a, bool staged_store) {
     if (a.stat_flag) *a.stat_flag = on ? 1 : 0;
 }
 
+// ---- launch report (cfgpp_igemm_last_launch) ------------------------------------------------------------------------------
+// What the last igemm_launch ISSUED, after every fallback: written by each launch_* just before its kernel launch, zeroed at the
+// entry of igemm_launch (a refused call reports zeros).  Slots:
+//   0 kernel family (1 igemm_kernel, 2 tile32_kernel, 3 igemm16_kernel, 4 big4_kernel, 5 big4p_kernel)   1 BM   2 BN   3 LDS stages
+//   4 AMODE as instantiated   5 operand staging (1 LDS-DMA, 0 registers)   6 grid (workgroups of the GEMM kernel)
+//   7 ksplit (1 = whole tiles)   8 n_major as finally set   9 walk_bn (0 = 1-D walk)   10 par_nb   11 dynamic LDS bytes
+//   12 producer statistics written (1 / 0)   13 epilogue variant (0 generic, 1 staged store, 2 staged GEGLU, 3 staged heads)
+//   14, 15 waves of the workgroup along M, along N
+static int g_last_launch[16] = {0};
+extern "C" void cfgpp_igemm_last_launch(int* out16) { for (int i = 0; i < 16; ++i) out16[i] = g_last_launch[i]; }
+// The epilogue variant igemm_kernel / tile32_kernel take for this launch: the predicates of the kernels' epilogue dispatch, with
+// the tile's constants (stage_bytes_all = NST * STAGE_BYTES, the LDS the staged forms may use).  K-split tiles finish in
+// igemm_reduce_kernel, which has the generic epilogue only.
+static int epi_variant(const IGemmArgs& a, int WM, int WN, int WTM, int WTN, int stage_bytes_all) {
+    if (a.ksplit > 1) return 0;
+    const int NW = WM * WN, MT = WTM / 32, NT = WTN / 32;
+    const bool staged_fits = NW * 32 * (WTN * 2 + 16) <= stage_bytes_all;
+    if (staged_fits && a.epi == EPI_STORE && (a.N & 7) == 0 && a.staged_epi) return 1;
+    if (NT % 2 == 0 && a.epi == EPI_GEGLU && (a.N & 127) == 0 && a.staged_epi && a.omode == 0) return 2;
+    const bool heads_fits = NW * NT * 2560 <= stage_bytes_all && MT * NT <= 8;
+    if (heads_fits && a.epi == EPI_HEADS && a.staged_epi && (a.rows_per_batch & 31) == 0 && (a.part_width & 31) == 0 && (a.head_dim & 7) == 0 &&
+        (a.N & 31) == 0 && (a.M & 31) == 0) return 3;
+    return 0;
+}
+// ... and of the families that have staged epilogues only (igemm16_kernel, big4_kernel, big4p_kernel: their admission tests)
+static int epi_variant_staged_only(const IGemmArgs& a) { return a.epi == EPI_STORE ? 1 : a.epi == EPI_GEGLU ? 2 : 3; }
+static void report_launch(int family, int BM, int BN, int NST, int amode, int dma, int grid, const IGemmArgs& a, int smem, int variant, int WM, int WN) {
+    const int r[16] = {family, BM, BN, NST, amode, dma, grid, a.ksplit, a.n_major, a.walk_bn, a.par_nb, smem, a.gstat != nullptr ? 1 : 0, variant, WM, WN};
+    for (int i = 0; i < 16; ++i) g_last_launch[i] = r[i];
+}
+
 template <int WM, int WN, int WTM, int WTN, bool GLDS, int AMODE, int NST = 2>
 int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     constexpr int BM = WM * WTM, BN = WN * WTN, NTHR = 64 * WM * WN;
@@ -1325,6 +1356,9 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     constexpr int blocks_per_cu = (160 * 1024) / smem_std < 8 ? (160 * 1024) / smem_std : 8;
     constexpr int slots = 256 * blocks_per_cu;       // resident workgroups on 256 CUs
     IGemmArgs a = a_in;
+    // GEGLU needs (value | gate) pairs of 32-column accumulator tiles in one wave: the 32- and 160-wide wave tiles have no such
+    // epilogue instantiated and would store nothing.  Only a forced config gets here (the rule and the tuner never pick them).
+    if ((WTN / 32) % 2 != 0 && a.epi == EPI_GEGLU) { cfgpp_set_error("igemm: GEGLU on a %d x %d tile of %d-column wave tiles", BM, BN, WTN); return -2; }
     const int ntm = AMODE == 4 ? phase_view(a, BM) : cdiv(a.M, BM);
     a.par_nb = par_slots(a, BM);
     const int smem = NST * (BM + BN) * 128 + (GLDS ? par_bytes(BN, a.par_nb > PAR_NB ? a.par_nb : PAR_NB) : 0);
@@ -1375,6 +1409,7 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     a.walk_div = a.n_major ? ntm : cdiv(a.N, BN);
     walk_plan(a, BM, BN, ntm, cdiv(a.N, BN), smem);
     a.tl = tl_take(WM * 100 + WN * 10 + (GLDS ? 1 : 0), a.n_main + n_tail * a.ksplit, NTHR, BM, BN, NST, a);
+    report_launch(1, BM, BN, NST, AMODE, GLDS ? 1 : 0, a.n_main + n_tail * a.ksplit, a, smem, epi_variant(a, WM, WN, WTM, WTN, NST * (BM + BN) * 128), WM, WN);
     hipLaunchKernelGGL(kern, dim3(a.n_main + n_tail * a.ksplit), dim3(NTHR), smem, stream, a);
     if (n_tail > 0)
         hipLaunchKernelGGL((igemm_reduce_kernel<WM, WN, WTM, WTN>), dim3(n_tail, (WTM / 32) * (WTN / 32)), dim3(NTHR), 0, stream, a);
@@ -1427,6 +1462,7 @@ int launch_tile32_amode(const IGemmArgs& a_in, hipStream_t stream) {
     walk_plan(a, BM, BN, ntm, ntn, smem);
     stats_decide(a, NTHR / 64 * 32 * (WTN * 2 + 16) <= NST * (BM + BN) * 64 && a.staged_epi);
     a.tl = tl_take(3200 + WM * 100 + WN * 10, a.n_main, NTHR, BM, BN, NST, a);
+    report_launch(2, BM, BN, NST, AMODE, 1, a.n_main, a, smem, epi_variant(a, WM, WN, WTM, WTN, NST * (BM + BN) * 64), WM, WN);
     hipLaunchKernelGGL(kern, dim3(a.n_main), dim3(NTHR), smem, stream, a);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1482,6 +1518,7 @@ int launch_mf16_amode(const IGemmArgs& a_in, hipStream_t stream) {
     walk_plan(a, 128, 160, ntm, ntn, smem);
     stats_decide(a, true);
     a.tl = tl_take(16, a.n_main, 512, 128, 160, NST, a);
+    report_launch(3, 128, 160, NST, AMODE, 1, a.n_main, a, smem, epi_variant_staged_only(a), 4, 2);
     hipLaunchKernelGGL(kern, dim3(a.n_main), dim3(512), smem, stream, a);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
@@ -1519,6 +1556,7 @@ static int launch_big4(int cfg, const IGemmArgs& a_in, hipStream_t stream) {
     walk_plan(a, BM, BN, ntm, ntn, smem);
     stats_decide(a, true);
     a.tl = tl_take(4000 + cfg, a.n_main, 256, BM, BN, 2, a);
+    report_launch(4, BM, BN, 2, a.amode, 1, a.n_main, a, smem, epi_variant_staged_only(a), 2, 2);
     return big4_run(cfg, a, a.n_main, smem, stream);
 }
 
@@ -1535,6 +1573,7 @@ static int launch_big4p(const IGemmArgs& a_in, hipStream_t stream) {
     a.walk_div = a.n_major ? ntm : ntn;
     walk_plan(a, 256, 256, ntm, ntn, smem);
     stats_decide(a, true);
+    report_launch(5, 256, 256, 2, 0, 1, a.n_main < 256 ? a.n_main : 256, a, smem, epi_variant_staged_only(a), 2, 4);
     return big4p_run(a, a.n_main < 256 ? a.n_main : 256, smem, pb, stream);
 }
 
@@ -1585,22 +1624,23 @@ static int launch_config(int cfg, const IGemmArgs& a, hipStream_t stream) {
         // config 5 (same wave tiles, same LDS traffic per CU) cut into two halves that no longer share a barrier - while one half
         // waits for its tile or sits in its epilogue, the other half's waves have the matrix pipes (round 5).  Plain stores only
         // (ten accumulator tiles per wave: no staged head-major epilogue, no GEGLU pairs).
-        case 27: if (a.epi != EPI_STORE) return launch_tile32<2, 2, 64, 64, 3, 3>(a, stream);
+        case 27: if (a.epi != EPI_STORE) { g_last_hint_applied = 0; return launch_tile32<2, 2, 64, 64, 3, 3>(a, stream); }
                  return launch_tile32<2, 2, 64, 160, 2, 2>(a, stream);
-        case 20: if (a.epi == EPI_GEGLU) return launch_tile32<2, 4, 128, 64, 4, 2>(a, stream);       // (GEGLU needs 64-wide wave tiles)
+        case 20: if (a.epi == EPI_GEGLU) { g_last_hint_applied = 0; return launch_tile32<2, 4, 128, 64, 4, 2>(a, stream); }     // (GEGLU needs 64-wide wave tiles)
                  return launch_tile32<4, 2, 64, 160, 4, 2>(a, stream);     // 256 x 320, 8 waves, 147 KB
         // 128 x 160 as 8 waves of 32 x 80 on the 16x16x32 MFMA, 3 / 4 LDS stages (igemm16_kernel): plain-store launches with
         // N % 160 == 0 only - anything else falls back to the 4-wave 128 x 160 tile.  Not a tuner candidate (different k order).
-        case 18: return mf16_supports(a) ? launch_mf16<3>(a, stream) : launch_cfg<4, 1, 32, 160, true>(a, stream);
-        case 19: return mf16_supports(a) ? launch_mf16<4>(a, stream) : launch_cfg<4, 1, 32, 160, true>(a, stream);
+        // (every fallback below reports "the config that was asked for did not run": cfgpp_igemm_last_config_ran)
+        case 18: case 19: if (!mf16_supports(a)) { g_last_hint_applied = 0; return launch_cfg<4, 1, 32, 160, true>(a, stream); }
+                 return cfg == 18 ? launch_mf16<3>(a, stream) : launch_mf16<4>(a, stream);
         // one wave per SIMD (big4_kernel.hip); launches they do not admit (generic epilogues, > 4 GiB operands) take the 128 x 128 tile
         // (no 2x2 phase form, amode 4, in that family: the candidate did not run)
-        case 24: case 25: case 26: if (a.amode == 4) g_last_hint_applied = 0;
-                 return big4_ok(cfg, a) ? launch_big4(cfg, a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
+        case 24: case 25: case 26: if (!big4_ok(cfg, a)) { g_last_hint_applied = 0; return launch_cfg<2, 2, 64, 64, true>(a, stream); }
+                 return launch_big4(cfg, a, stream);
         // the 256 x 256 one-wave-per-SIMD tile as a persistent kernel with the next output tile's first K-tile prefetched under the
         // epilogue (big4p_kernel.hip): token-major linears only
-        case 28: if (a.amode == 4) g_last_hint_applied = 0;
-                 return big4p_ok(a) ? launch_big4p(a, stream) : launch_cfg<2, 2, 64, 64, true>(a, stream);
+        case 28: if (!big4p_ok(a)) { g_last_hint_applied = 0; return launch_cfg<2, 2, 64, 64, true>(a, stream); }
+                 return launch_big4p(a, stream);
         default: cfgpp_set_error("igemm: bad config %d", cfg); return -2;
     }
 }
@@ -1667,6 +1707,7 @@ int igemm_upsample_phase_enabled() { return g_upsample_phase; }
 int igemm_launch(const IGemmArgs& a_in, hipStream_t stream) {
     IGemmArgs a = a_in;
     g_last_amode = a.amode;
+    for (int i = 0; i < 16; ++i) g_last_launch[i] = 0;
     g_last_hint_applied = (a_in.cfg_hint & 63) == 0 ? 1 : 0;
     a.allow_split = 1;
     a.tl = nullptr;

@@ -1329,6 +1329,21 @@ int cfgpp_op_igemm(const void* a0, const void* a1, int C0, int C1, int taps, int
     return igemm_launch(a, (hipStream_t)stream);
 }
 
+// cfgpp_op_igemm plus the arguments it cannot pass: ashift (amode 2), out_scale and the tuner's cfg_hint
+int cfgpp_op_igemm_ex(const void* a0, const void* a1, int C0, int C1, int taps, int amode, int H, int W,
+                      const void* w, int M, int N, const float* bias, const float* temb, int temb_ld,
+                      const void* resid, int rmode, int rld, void* out, int omode, int old_, int epi,
+                      int ashift, float out_scale, int cfg_hint, void* stream) {
+    IGemmArgs a = base_args();
+    a.a0 = (const half_t*)a0; a.a1 = (const half_t*)a1; a.C0 = C0; a.C1 = C1; a.taps = taps; a.amode = amode; a.H = H; a.W = W;
+    a.w = (const half_t*)w; a.M = M; a.N = N; a.K = taps * (C0 + C1); a.bias = bias; a.temb = temb; a.temb_ld = temb_ld;
+    a.rows_per_batch = H * W; a.resid = (const half_t*)resid; a.rmode = rmode; a.rld = rld;
+    a.out = (half_t*)out; a.omode = omode; a.old = old_; a.epi = epi;
+    a.ashift = ashift; a.out_scale = out_scale; a.cfg_hint = cfg_hint;
+    a.gstat = g_op_gstat; a.stat_flag = &g_op_gstat_flag; g_op_gstat_flag = 0;
+    return igemm_launch(a, (hipStream_t)stream);
+}
+
 int cfgpp_op_fold_upsample(const void* w9, void* w4, int O, int I, void* stream) {
     return igemm_fold_upsample_launch((const half_t*)w9, (half_t*)w4, O, I, (hipStream_t)stream);
 }
@@ -1358,3 +1373,15 @@ int cfgpp_op_igemm_heads(const void* a_, int K, const void* w, int M, int N, con
 }
 
 }  // extern "C"
+
+// cfgpp_op_igemm_heads plus vt_linear (V^T columns in natural key order, as the VAE's attention consumes them)
+int cfgpp_op_igemm_heads_ex(const void* a_, int K, const void* w, int M, int N, const float* bias, int rows_per_batch,
+                            void* hq, void* hk, void* hvt, int part0, int part_width, int head_dim, int heads,
+                            int q_tok_pad, int tok_pad, int vt_linear, void* stream) {
+    IGemmArgs a = base_args();
+    a.a0 = (const half_t*)a_; a.C0 = K; a.amode = 0; a.w = (const half_t*)w; a.M = M; a.N = N; a.K = K; a.bias = bias;
+    a.epi = EPI_HEADS; a.rows_per_batch = rows_per_batch; a.hq = (half_t*)hq; a.hk = (half_t*)hk; a.hvt = (half_t*)hvt;
+    a.part0 = part0; a.part_width = part_width; a.head_dim = head_dim; a.head_dim_pad = round_up(head_dim, 32);
+    a.heads = heads; a.q_tok_pad = q_tok_pad; a.tok_pad = tok_pad; a.vt_linear = vt_linear ? 1 : 0;
+    return igemm_launch(a, (hipStream_t)stream);
+}

@@ -80,6 +80,20 @@ def igemm(a0, a1, C0, C1, taps, amode, H, W, w, M, N, bias=None, temb=None, temb
     return out
 
 
+def igemm_ex(a0, a1, C0, C1, taps, amode, H, W, w, M, N, bias=None, temb=None, temb_ld=0, resid=None, rmode=0, rld=0,
+             out=None, omode=0, old=0, epi=0, ashift=0, out_scale=1.0, cfg_hint=0):
+    """cfgpp_op_igemm plus ashift, out_scale and the tuner's cfg_hint (cfgpp_debug.h)"""
+    check(lib().cfgpp_op_igemm_ex(P(a0), P(a1), C0, C1, taps, amode, H, W, P(w), M, N, P(bias), P(temb), temb_ld,
+                                  P(resid), rmode, rld, P(out), omode, old, epi, ashift, float(out_scale), cfg_hint, stream()),
+          "cfgpp_op_igemm_ex")
+    return out
+
+
+def igemm_last_launch():
+    """what the last implicit-GEMM launch issued, 16 slots (cfgpp_debug.h: cfgpp_igemm_last_launch)"""
+    return _last_launch("cfgpp_igemm_last_launch", 16)
+
+
 def linear(a, w, bias=None, resid=None, epi=0):
     M, K = a.shape
     N = w.shape[0]
