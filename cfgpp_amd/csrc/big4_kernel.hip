@@ -41,15 +41,8 @@ big4_kernel(const IGemmArgs p) {
     tl_begin(p.tl);
 
     // ---- workgroup -> tile (XCD-contiguous numbering, M- or N-major walk: as igemm_kernel) ----
-    int wg;
-    {
-        const int bid = blockIdx.x, nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
     int tile_m, tile_n;
-    tile_of(p, wg, tile_m, tile_n);
+    tile_of(p, xcd_contiguous(blockIdx.x, gridDim.x), tile_m, tile_n);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -65,19 +58,7 @@ big4_kernel(const IGemmArgs p) {
     int a_pix[QA];                 // pixel / token index of the lane's row (AMODE 3: packed (batch, y, x))
     unsigned a_off[QA], b_off[QB]; // byte offsets against the K-tile's scalar base
 #pragma unroll
-    for (int q = 0; q < QA; ++q) {
-        int m = m0 + (wid + 4 * q) * 8 + r8;
-        m = m < p.M ? m : p.M - 1;
-        if constexpr (AMODE == 0) a_pix[q] = m;
-        else if constexpr (AMODE == 1) a_pix[q] = padded_pix(m, HW, p.W, p.H);
-        else if constexpr (AMODE == 2) {
-            const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
-            a_pix[q] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
-        } else {
-            const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
-            a_pix[q] = (b << 22) | (y << 11) | x;
-        }
-    }
+    for (int q = 0; q < QA; ++q) a_pix[q] = a_row_map<AMODE>(p, m0 + (wid + 4 * q) * 8 + r8, HW, 0);      // (no amode 4 in this family)
 #pragma unroll
     for (int q = 0; q < QB; ++q) {
         int n = n0 + (wid + 4 * q) * 8 + r8;

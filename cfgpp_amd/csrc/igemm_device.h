@@ -1,6 +1,6 @@
 // Device-side helpers shared by the implicit-GEMM kernels (igemm_kernel.hip, big4_kernel.hip): timeline stamps, exact
-// small-quotient division, the epilogue-parameter segments in LDS, and every epilogue (plain, LDS-staged plain store,
-// GEGLU, head-major Q / K / V^T).  Header-only, anonymous namespace: each translation unit gets its own copy.
+// small-quotient division, the workgroup -> tile walk, the A-operand gather, the epilogue-parameter segments in LDS, and every
+// epilogue (plain, LDS-staged plain store, GEGLU, head-major Q / K / V^T) with the dispatch between them.  Header-only, anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "igemm.h"
 
@@ -65,6 +65,14 @@ __device__ __forceinline__ int phase_src_pix(int m, int HW, int W, int H, int ph
 }
 
 
+// XCD-contiguous numbering: block bid of nwg runs on XCD bid % 8; the blocks of one XCD get consecutive indices, so neighbours
+// (which share activation rows or a weight slab) meet in one XCD's L2
+__device__ __forceinline__ int xcd_contiguous(int bid, int nwg) {
+    const int q = nwg >> 3, r = nwg & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+}
+
 // workgroup index (XCD-contiguous numbering) -> tile.  Everything here is wave-uniform: the quotients go back to SGPRs
 // (readfirstlane), so the blocked form costs no vector registers beyond the prologue.
 __device__ __forceinline__ int qdiv_u(int a, int d) { return __builtin_amdgcn_readfirstlane(qdiv(a, d)); }
@@ -91,6 +99,54 @@ __device__ __forceinline__ int phase_of(const IGemmArgs& p, int& tile_m) {
         return ph;
     } else {
         return 0;
+    }
+}
+
+// ---- the A-operand gather ------------------------------------------------------------------------------------------------
+// Output row m (clamped to the last row: ragged M edges load valid memory and are masked at the store) -> the loader row's
+// pixel: a token row (amode 0), a halo-padded pixel (1: conv3x3 / conv1x1; 2: stride 2, on the 2H x 2W map; 4: the phase's
+// first tap on the source map) or packed (batch, y, x) that a_gather_pix unpacks per tap (3: fused nearest-2x upsample).
+template <int AMODE>
+__device__ __forceinline__ int a_row_map(const IGemmArgs& p, int m, int HW, int phase) {
+    m = m < p.M ? m : p.M - 1;
+    if constexpr (AMODE == 0) return m;
+    else if constexpr (AMODE == 1) return padded_pix(m, HW, p.W, p.H);
+    else if constexpr (AMODE == 4) return phase_src_pix(m, HW, p.W, p.H, phase);
+    else {
+        const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
+        if constexpr (AMODE == 2) return (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
+        else return (b << 22) | (y << 11) | x;
+    }
+}
+// 64-deep K-tile kt64 -> concat source, first channel inside it, channels per pixel, and the tap as (dy, dx) / pixel delta.
+// All of it is wave-uniform.
+struct Gather { const half_t* src; int cs, Cs, dpix, dy, dx; };
+template <int AMODE>
+__device__ __forceinline__ Gather a_gather(const IGemmArgs& p, int kt64) {
+    Gather g;
+    int tap = 0, cc = kt64 << 6;
+    if constexpr (AMODE == 4) { tap = kt64 & 3; cc = (kt64 >> 2) << 6; }
+    else if (p.taps == 9) { const int cb = kt64 / 9; tap = kt64 - cb * 9; cc = cb << 6; }
+    const bool s0 = cc < p.C0;
+    g.src = s0 ? p.a0 : p.a1;
+    g.cs = s0 ? cc : cc - p.C0; g.Cs = s0 ? p.C0 : p.C1;
+    g.dy = 0; g.dx = 0;
+    if (p.taps == 9) { g.dy = tap / 3 - 1; g.dx = tap - (tap / 3) * 3 - 1; }
+    g.dpix = 0;
+    if constexpr (AMODE == 1) g.dpix = g.dy * (p.W + 2) + g.dx;
+    else if constexpr (AMODE == 2) g.dpix = g.dy * (2 * p.W + 2) + g.dx;
+    else if constexpr (AMODE == 4) g.dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
+    return g;
+}
+// the pixel of g.src a loader row reads for that K-tile
+template <int AMODE>
+__device__ __forceinline__ int a_gather_pix(const IGemmArgs& p, int a_pix, const Gather& g) {
+    if constexpr (AMODE == 3) {
+        const int b = a_pix >> 22, y = (a_pix >> 11) & 2047, x = a_pix & 2047;
+        const int Hs = p.H >> 1, Ws = p.W >> 1;
+        return (b * (Hs + 2) + ((y + g.dy) >> 1) + 1) * (Ws + 2) + ((x + g.dx) >> 1) + 1;
+    } else {
+        return a_pix + g.dpix;
     }
 }
 
@@ -560,6 +616,46 @@ __device__ __forceinline__ void igemm_epilogue_heads_staged(const IGemmArgs& p, 
             }
         }
     }
+}
+
+// ---- epilogue dispatch of igemm_kernel / tile32_kernel ---------------------------------------------------------------------
+// What a tile of NW waves of MT x NT accumulator tiles with lds_bytes of free LDS CAN stage (compile-time) ...
+__host__ __device__ constexpr bool epi_store_fits(int NW, int NT, int lds_bytes) { return NW * 32 * (NT * 64 + 16) <= lds_bytes; }      // (256 x 320 with 32 x 320 waves: 164 KB, no)
+__host__ __device__ constexpr bool epi_geglu_fits(int NT) { return NT % 2 == 0; }
+__host__ __device__ constexpr bool epi_heads_fits(int NW, int MT, int NT, int lds_bytes) { return NW * NT * 2560 <= lds_bytes && MT * NT <= 8; }
+// ... and whether the launch takes it (run-time).  The kernels dispatch on these, in this order, and the launch report prints
+// the outcome (epi_variant).
+__host__ __device__ __forceinline__ bool epi_takes_store(const IGemmArgs& a, bool fits) {
+    return fits && a.epi == EPI_STORE && (a.N & 7) == 0 && a.staged_epi;
+}
+__host__ __device__ __forceinline__ bool epi_takes_geglu(const IGemmArgs& a, bool fits) {
+    return fits && a.epi == EPI_GEGLU && (a.N & 127) == 0 && a.staged_epi && a.omode == 0;
+}
+__host__ __device__ __forceinline__ bool epi_takes_heads(const IGemmArgs& a, bool fits) {
+    return fits && a.epi == EPI_HEADS && a.staged_epi && (a.rows_per_batch & 31) == 0 && (a.part_width & 31) == 0 &&
+           (a.head_dim & 7) == 0 && (a.N & 31) == 0 && (a.M & 31) == 0;
+}
+// lds = LDS_BYTES free bytes (the k-loop ended with a barrier: every wave is done with the tile stages); each wave stages in
+// its own region of it
+template <int NW, int MT, int NT, bool L, int AMODE, int LDS_BYTES>
+__device__ __forceinline__ void igemm_epilogue_dispatch(const IGemmArgs& p, f32x16 (&acc)[MT][NT], int mw0, int nw0, int lane, int wid,
+                                                        char* lds, const Par& par) {
+    if (epi_takes_store(p, epi_store_fits(NW, NT, LDS_BYTES))) {
+        igemm_epilogue_staged<MT, NT, L, false, AMODE>(p, acc, mw0, nw0, lane, lds + wid * (32 * (NT * 64 + 16)), par);
+        return;
+    }
+    if constexpr (epi_geglu_fits(NT)) {
+        if (epi_takes_geglu(p, true)) {
+            igemm_epilogue_geglu_staged<MT, NT, L>(p, acc, mw0, nw0, lane, lds + wid * (32 * ((NT / 2) * 64 + 16)), par);
+            return;
+        }
+    }
+    // (not instantiated for the 10-accumulator-tile waves: it pushed the 256 x 320 kernel into scratch spills)
+    if constexpr (epi_heads_fits(NW, MT, NT, LDS_BYTES)) if (epi_takes_heads(p, true)) {
+        igemm_epilogue_heads_staged<MT, NT, L>(p, acc, mw0, nw0, lane, lds + wid * (NT * 2560), par);
+        return;
+    }
+    igemm_epilogue<MT, NT, L, AMODE>(p, acc, mw0, nw0, lane, par);
 }
 
 }  // namespace

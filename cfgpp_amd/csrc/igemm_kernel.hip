@@ -57,22 +57,15 @@ igemm_kernel(const IGemmArgs p) {
     // K-split TAIL: tile n_main + b/ksplit, k-slice b % ksplit; they write fp32 partials that
     // igemm_reduce_kernel finishes.  (Tile quantisation, not the inner loop, is what the profile showed
     // to cost most: e.g. 640 tiles on 512 resident slots, or 80 tiles on 256 CUs.)
-    const int ntn = (p.N + BN - 1) / BN;
     const int bid = blockIdx.x;
     int wg, ksl = 0;
     const bool is_tail = bid >= p.n_main;
     if (!is_tail) {
-        const int nwg = p.n_main;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        wg = xcd_contiguous(bid, p.n_main);
     } else {
         // same XCD-contiguous numbering over the (tile, k-slice) pairs: the k-slices of neighbouring tiles (which share
         // activation rows / weight slabs slice by slice) meet in one XCD's L2
-        const int b1 = bid - p.n_main, nb = (int)gridDim.x - p.n_main;
-        const int q = nb >> 3, r = nb & 7;
-        const int xcd = b1 & 7, idx = b1 >> 3;
-        const int b2 = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        const int b2 = xcd_contiguous(bid - p.n_main, (int)gridDim.x - p.n_main);
         wg = p.n_main + b2 / p.ksplit;
         ksl = b2 - (b2 / p.ksplit) * p.ksplit;
     }
@@ -93,24 +86,9 @@ igemm_kernel(const IGemmArgs p) {
     // ---- loader state ----
     const int lrow = tid >> 3, lchunk = tid & 7;
     const int HW = p.rows_per_batch;
-    const int Cin = p.C0 + p.C1;
     int a_pix[A_CH];
 #pragma unroll
-    for (int j = 0; j < A_CH; ++j) {
-        int m = m0 + lrow + j * RSTEP;
-        m = m < p.M ? m : p.M - 1;
-        if constexpr (AMODE == 0) a_pix[j] = m;
-        else if constexpr (AMODE == 1) a_pix[j] = padded_pix(m, HW, p.W, p.H);
-        else if constexpr (AMODE == 2) {
-            const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
-            a_pix[j] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
-        } else if constexpr (AMODE == 4) {
-            a_pix[j] = phase_src_pix(m, HW, p.W, p.H, phase);
-        } else {
-            const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
-            a_pix[j] = (b << 22) | (y << 11) | x;      // unpacked per tap
-        }
-    }
+    for (int j = 0; j < A_CH; ++j) a_pix[j] = a_row_map<AMODE>(p, m0 + lrow + j * RSTEP, HW, phase);
     // source chunk: register staging loads logical chunk `lchunk` and swizzles the LDS store address;
     // the DMA path stores linearly, so it loads the chunk that BELONGS at physical slot `lchunk`.
     const int schunk = GLDS ? (lchunk ^ ((lrow >> 1) & 7)) : lchunk;
@@ -135,68 +113,46 @@ igemm_kernel(const IGemmArgs p) {
     const int kt_end = is_tail ? (int)(((long)(ksl + 1) * KT_all) / p.ksplit) : KT_all;
 
     auto load_tile = [&](int kt) {
-        int tap = 0, cc = kt << 6;
-        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
-        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
-        const bool s0 = cc < p.C0;
-        const half_t* src = s0 ? p.a0 : p.a1;
-        const int cs = s0 ? cc : cc - p.C0, Cs = s0 ? p.C0 : p.C1;
-        int dy = 0, dx = 0;
-        if (p.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
-        int dpix = 0;
-        if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
-        else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
-        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
+        const Gather g = a_gather<AMODE>(p, kt);
 #pragma unroll
-        for (int j = 0; j < A_CH; ++j) {
-            int pix;
-            if constexpr (AMODE == 3) {
-                const int b = a_pix[j] >> 22, y = (a_pix[j] >> 11) & 2047, x = a_pix[j] & 2047;
-                const int Hs = p.H >> 1, Ws = p.W >> 1;
-                pix = (b * (Hs + 2) + ((y + dy) >> 1) + 1) * (Ws + 2) + ((x + dx) >> 1) + 1;
-            } else {
-                pix = a_pix[j] + dpix;
-            }
-            ra[j] = *reinterpret_cast<const half8_t*>(src + (long)pix * Cs + cs + lchunk * 8);
-        }
+        for (int j = 0; j < A_CH; ++j)
+            ra[j] = *reinterpret_cast<const half8_t*>(g.src + (long)a_gather_pix<AMODE>(p, a_pix[j], g) * g.Cs + g.cs + lchunk * 8);
 #pragma unroll
         for (int j = 0; j < B_CH; ++j) rb[j] = *reinterpret_cast<const half8_t*>(b_ptr[j] + ((long)kt << 6));
     };
-    // DMA variant: same addresses, destination = wave-uniform LDS base (+ lane*16 added by hardware)
+    // DMA variant: same addresses, destination = wave-uniform LDS base (+ lane*16 added by hardware).  Piece q of K-tile kt
+    // into `stage`: q < A_CH an activation pass, else a weight pass (q compile-time after unrolling)
     const int wave_row0 = __builtin_amdgcn_readfirstlane(wid) * 8;
+    auto piece = [&](int q, int kt, int stage, const Gather& g) {
+        char* As = smem + stage * STAGE_BYTES;
+        char* Bs = As + BM * 128;
+        if (q < A_CH) {
+            const half_t* gp = g.src + (long)a_gather_pix<AMODE>(p, a_pix[q], g) * g.Cs + g.cs + schunk * 8;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
+                                             (__attribute__((address_space(3))) void*)(As + (wave_row0 + q * RSTEP) * 128), 16, 0, 0);
+        } else {
+            const int j = q - A_CH;
+            const half_t* gp = b_ptr[j] + ((long)kt << 6);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
+                                             (__attribute__((address_space(3))) void*)(Bs + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
+        }
+    };
+    // all of the wave's pieces of K-tile kt back to back (prologue).  (Written out rather than a loop over piece(): that form
+    //  cost the 256 x 256 kernel's fused-upsample instantiation 3 VGPRs)
     auto dma_tile = [&](int kt, int stage) {
-        int tap = 0, cc = kt << 6;
-        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
-        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
-        const bool s0 = cc < p.C0;
-        const half_t* src = s0 ? p.a0 : p.a1;
-        const int cs = s0 ? cc : cc - p.C0, Cs = s0 ? p.C0 : p.C1;
-        int dy = 0, dx = 0;
-        if (p.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
-        int dpix = 0;
-        if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
-        else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
-        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
+        const Gather g = a_gather<AMODE>(p, kt);
         char* As = smem + stage * STAGE_BYTES;
         char* Bs = As + BM * 128;
 #pragma unroll
         for (int j = 0; j < A_CH; ++j) {
-            int pix;
-            if constexpr (AMODE == 3) {
-                const int b = a_pix[j] >> 22, y = (a_pix[j] >> 11) & 2047, x = a_pix[j] & 2047;
-                const int Hs = p.H >> 1, Ws = p.W >> 1;
-                pix = (b * (Hs + 2) + ((y + dy) >> 1) + 1) * (Ws + 2) + ((x + dx) >> 1) + 1;
-            } else {
-                pix = a_pix[j] + dpix;
-            }
-            const half_t* g = src + (long)pix * Cs + cs + schunk * 8;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+            const half_t* gp = g.src + (long)a_gather_pix<AMODE>(p, a_pix[j], g) * g.Cs + g.cs + schunk * 8;
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
                                              (__attribute__((address_space(3))) void*)(As + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < B_CH; ++j) {
-            const half_t* g = b_ptr[j] + ((long)kt << 6);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+            const half_t* gp = b_ptr[j] + ((long)kt << 6);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
                                              (__attribute__((address_space(3))) void*)(Bs + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
         }
     };
@@ -255,47 +211,12 @@ igemm_kernel(const IGemmArgs p) {
             constexpr bool DMA = decltype(with_dma)::value;
             const char* As = smem + cur * STAGE_BYTES;
             const char* Bs = As + BM * 128;
-            // per-tile scalars of the NEXT tile's gather
-            const half_t* src = p.a0; int cs = 0, Cs = p.C0, dpix = 0, dy = 0, dx = 0;
-            char* Asn = smem + nxt * STAGE_BYTES;
-            char* Bsn = Asn + BM * 128;
-            if constexpr (DMA) {
-                int tap = 0, cc = ktn << 6;
-                if constexpr (AMODE == 4) { tap = ktn & 3; cc = (ktn >> 2) << 6; }
-                else if (p.taps == 9) { const int cb = ktn / 9; tap = ktn - cb * 9; cc = cb << 6; }
-                const bool s0 = cc < p.C0;
-                src = s0 ? p.a0 : p.a1;
-                cs = s0 ? cc : cc - p.C0; Cs = s0 ? p.C0 : p.C1;
-                if (p.taps == 9) { dy = tap / 3 - 1; dx = tap - (tap / 3) * 3 - 1; }
-                if constexpr (AMODE == 1) dpix = dy * (p.W + 2) + dx;
-                else if constexpr (AMODE == 2) dpix = dy * (2 * p.W + 2) + dx;
-        else if constexpr (AMODE == 4) dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
-            }
-            auto piece = [&](int q) {
-                if (q < A_CH) {
-                    const int j = q;
-                    int pix;
-                    if constexpr (AMODE == 3) {
-                        const int b = a_pix[j] >> 22, y = (a_pix[j] >> 11) & 2047, x = a_pix[j] & 2047;
-                        const int Hs = p.H >> 1, Ws = p.W >> 1;
-                        pix = (b * (Hs + 2) + ((y + dy) >> 1) + 1) * (Ws + 2) + ((x + dx) >> 1) + 1;
-                    } else {
-                        pix = a_pix[j] + dpix;
-                    }
-                    const half_t* g = src + (long)pix * Cs + cs + schunk * 8;
-                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                     (__attribute__((address_space(3))) void*)(Asn + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
-                } else {
-                    const int j = q - A_CH;
-                    const half_t* g = b_ptr[j] + ((long)ktn << 6);
-                            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                                     (__attribute__((address_space(3))) void*)(Bsn + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
-                }
-            };
+            Gather gn = {p.a0, 0, p.C0, 0, 0, 0};      // per-tile scalars of the NEXT tile's gather
+            if constexpr (DMA) gn = a_gather<AMODE>(p, ktn);
             int issued = 0, done = 0;                 // compile-time after unrolling
             if constexpr (DMA && !ILV) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) piece(q);
+                for (int q = 0; q < NP; ++q) piece(q, ktn, nxt, gn);
                 issued = NP;
             }
             auto after_mfma = [&]() {
@@ -303,7 +224,7 @@ igemm_kernel(const IGemmArgs p) {
                 if constexpr (DMA && ILV) {
                     if (issued < NP && done * NP >= (issued + 1) * SPAN) {
                         __builtin_amdgcn_sched_barrier(0);
-                        piece(issued); ++issued;
+                        piece(issued, ktn, nxt, gn); ++issued;
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -360,7 +281,7 @@ igemm_kernel(const IGemmArgs p) {
             }
             if constexpr (DMA) {
 #pragma unroll
-                for (int q = 0; q < NP; ++q) if (q >= issued) piece(q);      // (none when SPAN <= NM)
+                for (int q = 0; q < NP; ++q) if (q >= issued) piece(q, ktn, nxt, gn);      // (none when SPAN <= NM)
             }
             if constexpr (NST == 2) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -385,62 +306,62 @@ igemm_kernel(const IGemmArgs p) {
     } else {
         load_tile(kt_begin);
         store_tile(0);
-    __syncthreads();
-    for (int kt = kt_begin; kt < kt_end; ++kt) {
-        const int cur = (kt - kt_begin) & 1;
-        if (kt + 1 < kt_end) {
-            load_tile(kt + 1);
-        }
-        const char* As = smem + cur * STAGE_BYTES;
-        const char* Bs = As + BM * 128;
-        if constexpr (MT * NT <= 8) {
-            // fragment reads are software-pipelined one k-step ahead of the MFMAs that consume them
-            half8_t xa[2][MT], wb[2][NT];
-            {
-                const int coff = ((0 | fhi) ^ fsw) << 4;
+        __syncthreads();
+        for (int kt = kt_begin; kt < kt_end; ++kt) {
+            const int cur = (kt - kt_begin) & 1;
+            if (kt + 1 < kt_end) load_tile(kt + 1);
+            const char* As = smem + cur * STAGE_BYTES;
+            const char* Bs = As + BM * 128;
+            // (the k-step of the DMA path, without its after_mfma() hook.  Written out twice on purpose: shared through one lambda
+            //  or device function taking the hook - six forms were compiled - the 8 x 1 and 4 x 2 tiles of 32 x 320 / 32 x 160 waves
+            //  took one VGPR more, the 8 x 1 one reaching 256)
+            if constexpr (MT * NT <= 8) {
+                // fragment reads are software-pipelined one k-step ahead of the MFMAs that consume them
+                half8_t xa[2][MT], wb[2][NT];
+                {
+                    const int coff = ((0 | fhi) ^ fsw) << 4;
 #pragma unroll
-                for (int i = 0; i < MT; ++i) xa[0][i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
+                    for (int i = 0; i < MT; ++i) xa[0][i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
 #pragma unroll
-                for (int j = 0; j < NT; ++j) wb[0][j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
-            }
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                if (ks < 3) {
-                    const int coff = ((((ks + 1) << 1) | fhi) ^ fsw) << 4;
-#pragma unroll
-                    for (int i = 0; i < MT; ++i) xa[(ks + 1) & 1][i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
-#pragma unroll
-                    for (int j = 0; j < NT; ++j) wb[(ks + 1) & 1][j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
+                    for (int j = 0; j < NT; ++j) wb[0][j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
                 }
 #pragma unroll
-                for (int i = 0; i < MT; ++i)
+                for (int ks = 0; ks < 4; ++ks) {
+                    if (ks < 3) {
+                        const int coff = ((((ks + 1) << 1) | fhi) ^ fsw) << 4;
 #pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[ks & 1][j], xa[ks & 1][i], acc[i][j], 0, 0, 0);
+                        for (int i = 0; i < MT; ++i) xa[(ks + 1) & 1][i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
+#pragma unroll
+                        for (int j = 0; j < NT; ++j) wb[(ks + 1) & 1][j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
+                    }
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[ks & 1][j], xa[ks & 1][i], acc[i][j], 0, 0, 0);
+                }
+            } else {
+                // 10 accumulator tiles per wave (256x320): no room for a second fragment set; 10 MFMAs per k-step
+                // (320 cycles) give the partner wave on the SIMD time to cover the LDS latency instead
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) {
+                    const int coff = (((ks << 1) | fhi) ^ fsw) << 4;
+                    half8_t xa[MT], wb[NT];
+#pragma unroll
+                    for (int i = 0; i < MT; ++i) xa[i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) wb[j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
+#pragma unroll
+                    for (int i = 0; i < MT; ++i)
+#pragma unroll
+                        for (int j = 0; j < NT; ++j)
+                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[j], xa[i], acc[i][j], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);      // keep one fragment set live: no hoisting of the next k-step's reads
+                }
             }
-        } else {
-            // 10 accumulator tiles per wave (256x320): no room for a second fragment set; 10 MFMAs per k-step
-            // (320 cycles) give the partner wave on the SIMD time to cover the LDS latency instead
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int coff = (((ks << 1) | fhi) ^ fsw) << 4;
-                half8_t xa[MT], wb[NT];
-#pragma unroll
-                for (int i = 0; i < MT; ++i) xa[i] = *reinterpret_cast<const half8_t*>(As + a_rd + i * 32 * 128 + coff);
-#pragma unroll
-                for (int j = 0; j < NT; ++j) wb[j] = *reinterpret_cast<const half8_t*>(Bs + b_rd + j * 32 * 128 + coff);
-#pragma unroll
-                for (int i = 0; i < MT; ++i)
-#pragma unroll
-                    for (int j = 0; j < NT; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wb[j], xa[i], acc[i][j], 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);      // keep one fragment set live: no hoisting of the next k-step's reads
-            }
+            if (kt + 1 < kt_end) store_tile(cur ^ 1);
+            __syncthreads();
         }
-        if (kt + 1 < kt_end) store_tile(cur ^ 1);
-        __syncthreads();
-    }
-
     }
 
     const int mw0 = m0 + wm * WTM, nw0 = n0 + wn * WTN;
@@ -458,29 +379,7 @@ igemm_kernel(const IGemmArgs p) {
     }
     Par par;
     par.lds = GLDS ? smem + PAR_OFF : nullptr; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN); par.phase = phase;
-    constexpr bool STAGED_FITS = WM * WN * 32 * (WTN * 2 + 16) <= NST * STAGE_BYTES;      // (256 x 320 with 32 x 320 waves: 164 KB, no)
-    if (STAGED_FITS && p.epi == EPI_STORE && (p.N & 7) == 0 && p.staged_epi) {
-        // the k-loop ended with a barrier: every wave is done with the tile stages, LDS is free
-        igemm_epilogue_staged<MT, NT, GLDS, false, AMODE>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
-        tl_end(p.tl);
-        return;
-    }
-    if constexpr (NT % 2 == 0) {
-        if (p.epi == EPI_GEGLU && (p.N & 127) == 0 && p.staged_epi && p.omode == 0) {
-            igemm_epilogue_geglu_staged<MT, NT, GLDS>(p, acc, mw0, nw0, lane, smem + wid * (32 * ((NT / 2) * 64 + 16)), par);
-            tl_end(p.tl);
-            return;
-        }
-    }
-    // (not instantiated for the 10-accumulator-tile waves: it pushed the 256 x 320 kernel into scratch spills)
-    constexpr bool HEADS_FITS = WM * WN * NT * 2560 <= NST * STAGE_BYTES && MT * NT <= 8;
-    if constexpr (HEADS_FITS) if (p.epi == EPI_HEADS && p.staged_epi && (p.rows_per_batch & 31) == 0 && (p.part_width & 31) == 0 &&
-        (p.head_dim & 7) == 0 && (p.N & 31) == 0 && (p.M & 31) == 0) {
-        igemm_epilogue_heads_staged<MT, NT, GLDS>(p, acc, mw0, nw0, lane, smem + wid * (NT * 2560), par);
-        tl_end(p.tl);
-        return;
-    }
-    igemm_epilogue<MT, NT, GLDS, AMODE>(p, acc, mw0, nw0, lane, par);
+    igemm_epilogue_dispatch<WM * WN, MT, NT, GLDS, AMODE, NST * STAGE_BYTES>(p, acc, mw0, nw0, lane, wid, smem, par);
     tl_end(p.tl);
 }
 
@@ -549,22 +448,13 @@ tile32_kernel(const IGemmArgs p) {
     constexpr int MT = WTM / 32, NT = WTN / 32;
     constexpr int A_P = BM / 16, B_P = BN / 16, TOT = A_P + B_P;      // 16-row DMA pieces of the two operand tiles
     constexpr int FULL = TOT / NW, REM = TOT % NW, PPW = FULL + (REM ? 1 : 0);
-    constexpr int NM = 2 * MT * NT;                        // MFMAs per wave per K-tile
     constexpr int STAGE_BYTES = (BM + BN) * 64;
     constexpr int PAR_OFF = NST * STAGE_BYTES;             // epilogue parameters behind the ring
     extern __shared__ __attribute__((aligned(16))) char smem[];
     tl_begin(p.tl);
 
-    const int bid = blockIdx.x;
-    int wg;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
     int tile_m, tile_n;
-    tile_of(p, wg, tile_m, tile_n);
+    tile_of(p, xcd_contiguous(blockIdx.x, gridDim.x), tile_m, tile_n);
     const int phase = phase_of<AMODE>(p, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -585,19 +475,7 @@ tile32_kernel(const IGemmArgs p) {
         const int g = wid + NW * q;
         a_pix[q] = 0; b_ptr[q] = p.w;
         if (g < A_P) {
-            int m = m0 + g * 16 + prow;
-            m = m < p.M ? m : p.M - 1;
-            if constexpr (AMODE == 0) a_pix[q] = m;
-            else if constexpr (AMODE == 1) a_pix[q] = padded_pix(m, HW, p.W, p.H);
-            else if constexpr (AMODE == 2) {
-                const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
-                a_pix[q] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
-            } else if constexpr (AMODE == 4) {
-                a_pix[q] = phase_src_pix(m, HW, p.W, p.H, phase);
-            } else {
-                const int b = qdiv(m, HW), r2 = m - b * HW, y = qdiv(r2, p.W), x = r2 - y * p.W;
-                a_pix[q] = (b << 22) | (y << 11) | x;
-            }
+            a_pix[q] = a_row_map<AMODE>(p, m0 + g * 16 + prow, HW, phase);
             dst[q] = g * 16 * 64;
         } else {
             int n = n0 + (g - A_P) * 16 + prow;
@@ -606,37 +484,16 @@ tile32_kernel(const IGemmArgs p) {
             dst[q] = BM * 64 + (g - A_P) * 16 * 64;
         }
     }
-    struct Gather { const half_t* src; int cs, Cs, dpix, dy, dx; };
-    auto gather_of = [&](int kt) {                          // kt = 32-deep K-tile
-        Gather g;
-        const int k64 = kt >> 1;
-        int tap = 0, cc = k64 << 6;
-        if constexpr (AMODE == 4) { tap = k64 & 3; cc = (k64 >> 2) << 6; }
-        else if (p.taps == 9) { const int cb = k64 / 9; tap = k64 - cb * 9; cc = cb << 6; }
-        const bool s0 = cc < p.C0;
-        g.src = s0 ? p.a0 : p.a1;
-        g.cs = (s0 ? cc : cc - p.C0) + ((kt & 1) << 5); g.Cs = s0 ? p.C0 : p.C1;
-        g.dy = 0; g.dx = 0;
-        if (p.taps == 9) { g.dy = tap / 3 - 1; g.dx = tap - (tap / 3) * 3 - 1; }
-        g.dpix = 0;
-        if constexpr (AMODE == 1) g.dpix = g.dy * (p.W + 2) + g.dx;
-        else if constexpr (AMODE == 2) g.dpix = g.dy * (2 * p.W + 2) + g.dx;
-        else if constexpr (AMODE == 4) g.dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
+    auto gather_of = [&](int kt) {                          // kt = 32-deep K-tile: half (kt & 1) of 64-deep tile kt >> 1
+        Gather g = a_gather<AMODE>(p, kt >> 1);
+        g.cs += (kt & 1) << 5;
         return g;
     };
     auto piece = [&](int q, int kt, int stage, const Gather& g) {      // q compile-time after unrolling
         char* base = smem + stage * STAGE_BYTES;
         const int gi = wid + NW * q;
         if (gi < A_P) {
-            int pix;
-            if constexpr (AMODE == 3) {
-                const int b = a_pix[q] >> 22, y = (a_pix[q] >> 11) & 2047, x = a_pix[q] & 2047;
-                const int Hs = p.H >> 1, Ws = p.W >> 1;
-                pix = (b * (Hs + 2) + ((y + g.dy) >> 1) + 1) * (Ws + 2) + ((x + g.dx) >> 1) + 1;
-            } else {
-                pix = a_pix[q] + g.dpix;
-            }
-            const half_t* gp = g.src + (long)pix * g.Cs + g.cs + schunk * 8;
+            const half_t* gp = g.src + (long)a_gather_pix<AMODE>(p, a_pix[q], g) * g.Cs + g.cs + schunk * 8;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
                                              (__attribute__((address_space(3))) void*)(base + dst[q]), 16, 0, 0);
         } else {
@@ -763,27 +620,7 @@ tile32_kernel(const IGemmArgs p) {
     const int mw0 = m0 + wm * WTM, nw0 = n0 + wn * WTN;
     Par par;
     par.lds = smem + PAR_OFF; par.n0 = n0; par.b0 = HW > 0 ? qdiv(m0, HW) : 0; par.bnp = par_bnp(BN); par.phase = phase;
-    constexpr bool STAGED_FITS = NW * 32 * (WTN * 2 + 16) <= NST * STAGE_BYTES;
-    if (STAGED_FITS && p.epi == EPI_STORE && (p.N & 7) == 0 && p.staged_epi) {
-        igemm_epilogue_staged<MT, NT, true, false, AMODE>(p, acc, mw0, nw0, lane, smem + wid * (32 * (WTN * 2 + 16)), par);
-        tl_end(p.tl);
-        return;
-    }
-    if constexpr (NT % 2 == 0) {
-        if (p.epi == EPI_GEGLU && (p.N & 127) == 0 && p.staged_epi && p.omode == 0) {
-            igemm_epilogue_geglu_staged<MT, NT, true>(p, acc, mw0, nw0, lane, smem + wid * (32 * ((NT / 2) * 64 + 16)), par);
-            tl_end(p.tl);
-            return;
-        }
-    }
-    constexpr bool HEADS_FITS = NW * NT * 2560 <= NST * STAGE_BYTES && MT * NT <= 8;
-    if constexpr (HEADS_FITS) if (p.epi == EPI_HEADS && p.staged_epi && (p.rows_per_batch & 31) == 0 && (p.part_width & 31) == 0 &&
-        (p.head_dim & 7) == 0 && (p.N & 31) == 0 && (p.M & 31) == 0) {
-        igemm_epilogue_heads_staged<MT, NT, true>(p, acc, mw0, nw0, lane, smem + wid * (NT * 2560), par);
-        tl_end(p.tl);
-        return;
-    }
-    igemm_epilogue<MT, NT, true, AMODE>(p, acc, mw0, nw0, lane, par);
+    igemm_epilogue_dispatch<NW, MT, NT, true, AMODE, NST * STAGE_BYTES>(p, acc, mw0, nw0, lane, wid, smem, par);
     tl_end(p.tl);
 }
 
@@ -961,21 +798,12 @@ igemm16_kernel(const IGemmArgs p) {
     constexpr int BM = 128, BN = 160, RSTEP = 64;
     constexpr int A_CH = BM / RSTEP;                // 2 loader passes over the activation rows
     constexpr int STAGE_BYTES = (BM + BN) * 128;
-    constexpr int NM = 20;                          // MFMAs per wave per K-tile: 2 k-steps x (2 x 5) tiles
     static_assert(NST >= 3 && NST <= 4, "ring depth");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     tl_begin(p.tl);
 
-    const int bid = blockIdx.x;
-    int wg;
-    {
-        const int nwg = gridDim.x;
-        const int q = nwg >> 3, r = nwg & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
     int tile_m, tile_n;
-    tile_of(p, wg, tile_m, tile_n);
+    tile_of(p, xcd_contiguous(blockIdx.x, gridDim.x), tile_m, tile_n);
     const int phase = phase_of<AMODE>(p, tile_m);
     const int m0 = tile_m * BM, n0 = tile_n * BN;
 
@@ -989,21 +817,7 @@ igemm16_kernel(const IGemmArgs p) {
     const int HW = p.rows_per_batch;
     int a_pix[A_CH];
 #pragma unroll
-    for (int j = 0; j < A_CH; ++j) {
-        int m = m0 + lrow + j * RSTEP;
-        m = m < p.M ? m : p.M - 1;
-        if constexpr (AMODE == 0) a_pix[j] = m;
-        else if constexpr (AMODE == 1) a_pix[j] = padded_pix(m, HW, p.W, p.H);
-        else if constexpr (AMODE == 2) {
-            const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
-            a_pix[j] = (b * (2 * p.H + 2) + 2 * y + 1 + p.ashift) * (2 * p.W + 2) + 2 * x + 1 + p.ashift;
-        } else if constexpr (AMODE == 4) {
-            a_pix[j] = phase_src_pix(m, HW, p.W, p.H, phase);
-        } else {
-            const int b = qdiv(m, HW), q = m - b * HW, y = qdiv(q, p.W), x = q - y * p.W;
-            a_pix[j] = (b << 22) | (y << 11) | x;
-        }
-    }
+    for (int j = 0; j < A_CH; ++j) a_pix[j] = a_row_map<AMODE>(p, m0 + lrow + j * RSTEP, HW, phase);
     const int schunk = lchunk ^ ((lrow >> 1) & 7);  // the DMA stores lane-linear: swizzle the SOURCE chunk
     const half_t* b_ptr[3];
 #pragma unroll
@@ -1014,40 +828,14 @@ igemm16_kernel(const IGemmArgs p) {
     }
     const int wave_row0 = wid * 8;
 
-    struct Gather { const half_t* src; int cs, Cs, dpix, dy, dx; };
-    auto gather_of = [&](int kt) {
-        Gather g;
-        int tap = 0, cc = kt << 6;
-        if constexpr (AMODE == 4) { tap = kt & 3; cc = (kt >> 2) << 6; }
-        else if (p.taps == 9) { const int cb = kt / 9; tap = kt - cb * 9; cc = cb << 6; }
-        const bool s0 = cc < p.C0;
-        g.src = s0 ? p.a0 : p.a1;
-        g.cs = s0 ? cc : cc - p.C0; g.Cs = s0 ? p.C0 : p.C1;
-        g.dy = 0; g.dx = 0;
-        if (p.taps == 9) { g.dy = tap / 3 - 1; g.dx = tap - (tap / 3) * 3 - 1; }
-        g.dpix = 0;
-        if constexpr (AMODE == 1) g.dpix = g.dy * (p.W + 2) + g.dx;
-        else if constexpr (AMODE == 2) g.dpix = g.dy * (2 * p.W + 2) + g.dx;
-        else if constexpr (AMODE == 4) g.dpix = (tap >> 1) * (p.W + 2) + (tap & 1);
-        return g;
-    };
     // piece q of K-tile kt into `stage`: q = 0, 1 activation passes; 2, 3 weight passes; 4 the half weight pass (b3 waves)
     auto piece = [&](int q, int kt, int stage, const Gather& g) {
         char* As = smem + stage * STAGE_BYTES;
         char* Bs = As + BM * 128;
         if (q < A_CH) {
-            const int j = q;
-            int pix;
-            if constexpr (AMODE == 3) {
-                const int b = a_pix[j] >> 22, y = (a_pix[j] >> 11) & 2047, x = a_pix[j] & 2047;
-                const int Hs = p.H >> 1, Ws = p.W >> 1;
-                pix = (b * (Hs + 2) + ((y + g.dy) >> 1) + 1) * (Ws + 2) + ((x + g.dx) >> 1) + 1;
-            } else {
-                pix = a_pix[j] + g.dpix;
-            }
-            const half_t* gp = g.src + (long)pix * g.Cs + g.cs + schunk * 8;
+            const half_t* gp = g.src + (long)a_gather_pix<AMODE>(p, a_pix[q], g) * g.Cs + g.cs + schunk * 8;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp,
-                                             (__attribute__((address_space(3))) void*)(As + (wave_row0 + j * RSTEP) * 128), 16, 0, 0);
+                                             (__attribute__((address_space(3))) void*)(As + (wave_row0 + q * RSTEP) * 128), 16, 0, 0);
         } else {
             const int j = q - A_CH;
             const half_t* gp = b_ptr[j] + ((long)kt << 6);
@@ -1080,7 +868,7 @@ igemm16_kernel(const IGemmArgs p) {
 #pragma unroll
     for (int s_ = 0; s_ < NST - 1; ++s_)
         if (s_ < nk) {
-            const Gather g = gather_of(s_);
+            const Gather g = a_gather<AMODE>(p, s_);
 #pragma unroll
             for (int q = 0; q < 4; ++q) piece(q, s_, s_, g);
             if (b3) piece(4, s_, s_, g);
@@ -1121,7 +909,7 @@ igemm16_kernel(const IGemmArgs p) {
     auto tile_body = [&](int kt, int cur, int ktn, int nxt, auto with_dma) {
         constexpr bool DMA = decltype(with_dma)::value;
         Gather gn = {p.a0, 0, p.C0, 0, 0, 0};
-        if constexpr (DMA) gn = gather_of(ktn);
+        if constexpr (DMA) gn = a_gather<AMODE>(p, ktn);
         // phase s: ten MFMAs; after the first one the fragments of the NEXT phase are requested; the wave's DMA pieces go out
         // after every second MFMA of ITS phase
         auto phase = [&](auto s_tag) {
@@ -1317,6 +1105,40 @@ static void stats_decide(IGemmArgs& a, bool staged_store) {
     if (a.stat_flag) *a.stat_flag = on ? 1 : 0;
 }
 
+// ---- what every launcher does between sizing its grid (n_main, ksplit set) and launching ----------------------------------------
+// The tile walk - by operand bytes unless a switch or the tuner's pin says otherwise, then the blocked form if it pays - and the
+// producer-statistics decision (the two touch disjoint fields).  n_tail: K-split tiles of the launch.
+static void plan_walk(IGemmArgs& a, int BM, int BN, int ntm, int ntn, int smem, bool staged_store, int n_tail = 0) {
+    // weight bytes vs unique activation bytes (a 3x3 conv re-reads each pixel through L2: its A operand is M x Cin)
+    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
+    a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
+    if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
+    stats_decide(a, staged_store && n_tail == 0);
+    if (n_tail > 0) a.n_major = 0;                     // K-split tiles keep the M-major numbering the reduce kernel uses
+    a.walk_div = a.n_major ? ntm : ntn;
+    walk_plan(a, BM, BN, ntm, ntn, smem);
+}
+// a.amode as a compile-time tag: f(std::integral_constant<int, AMODE>)
+template <class F>
+static int with_amode(const IGemmArgs& a, F&& f) {
+    switch (a.amode) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
+    }
+}
+// dynamic-LDS limit of a kernel: raised when a launch needs more than any before it (high_water: one static per instantiation)
+static int lds_limit(const void* kern, int& high_water, int smem) {
+    if (smem > high_water) {
+        CFGPP_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        high_water = smem;
+    }
+    return 0;
+}
+
 // ---- launch report (cfgpp_igemm_last_launch) ------------------------------------------------------------------------------
 // What the last igemm_launch ISSUED, after every fallback: written by each launch_* just before its kernel launch, zeroed at the
 // entry of igemm_launch (a refused call reports zeros).  Slots:
@@ -1327,18 +1149,15 @@ static void stats_decide(IGemmArgs& a, bool staged_store) {
 //   14, 15 waves of the workgroup along M, along N
 static int g_last_launch[16] = {0};
 extern "C" void cfgpp_igemm_last_launch(int* out16) { for (int i = 0; i < 16; ++i) out16[i] = g_last_launch[i]; }
-// The epilogue variant igemm_kernel / tile32_kernel take for this launch: the predicates of the kernels' epilogue dispatch, with
-// the tile's constants (stage_bytes_all = NST * STAGE_BYTES, the LDS the staged forms may use).  K-split tiles finish in
+// The epilogue variant igemm_kernel / tile32_kernel take for this launch: igemm_epilogue_dispatch's own predicates, in its order,
+// with the tile's constants (stage_bytes_all = NST * STAGE_BYTES, the LDS the staged forms may use).  K-split tiles finish in
 // igemm_reduce_kernel, which has the generic epilogue only.
 static int epi_variant(const IGemmArgs& a, int WM, int WN, int WTM, int WTN, int stage_bytes_all) {
     if (a.ksplit > 1) return 0;
     const int NW = WM * WN, MT = WTM / 32, NT = WTN / 32;
-    const bool staged_fits = NW * 32 * (WTN * 2 + 16) <= stage_bytes_all;
-    if (staged_fits && a.epi == EPI_STORE && (a.N & 7) == 0 && a.staged_epi) return 1;
-    if (NT % 2 == 0 && a.epi == EPI_GEGLU && (a.N & 127) == 0 && a.staged_epi && a.omode == 0) return 2;
-    const bool heads_fits = NW * NT * 2560 <= stage_bytes_all && MT * NT <= 8;
-    if (heads_fits && a.epi == EPI_HEADS && a.staged_epi && (a.rows_per_batch & 31) == 0 && (a.part_width & 31) == 0 && (a.head_dim & 7) == 0 &&
-        (a.N & 31) == 0 && (a.M & 31) == 0) return 3;
+    if (epi_takes_store(a, epi_store_fits(NW, NT, stage_bytes_all))) return 1;
+    if (epi_takes_geglu(a, epi_geglu_fits(NT))) return 2;
+    if (epi_takes_heads(a, epi_heads_fits(NW, MT, NT, stage_bytes_all))) return 3;
     return 0;
 }
 // ... and of the families that have staged epilogues only (igemm16_kernel, big4_kernel, big4p_kernel: their admission tests)
@@ -1370,19 +1189,10 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
     }
     static int attr_smem = 0;
     auto kern = igemm_kernel<WM, WN, WTM, WTN, GLDS, AMODE, NST>;
-    if (smem > attr_smem) {
-        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_smem = smem;
-    }
-    const int T = ntm * cdiv(a.N, BN);
+    if (const int rc = lds_limit(reinterpret_cast<const void*>(kern), attr_smem, smem)) return rc;
+    const int ntn = cdiv(a.N, BN), T = ntm * ntn;
     const int KT = a.K >> 6;
     a.n_main = T; a.ksplit = 1; a.ws = nullptr; a.staged_epi = g_staged_epi;
-    {   // weight bytes vs unique activation bytes (a 3x3 conv re-reads each pixel through L2: its A operand is M x Cin)
-        const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
-        a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && cdiv(a.N, BN) >= 8)) ? 1 : 0;
-        if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
-    }
     // K-split: every tile is split S ways into fp32 partials (coalesced, register order) and igemm_reduce_kernel
     // finishes them.  (a) igemm_launch's big-tile rule / diagnostics pass S in IGemmArgs::split; (b) tiny grids with a
     // long K on the 64x64-wave tiles (the 8x8-level convs: 80 tiles on 256 CUs, K = 11520..23040): S is chosen so
@@ -1404,10 +1214,7 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
         }
     }
     const int n_tail = T - a.n_main;
-    stats_decide(a, WM * WN * 32 * (WTN * 2 + 16) <= NST * (BM + BN) * 128 && a.staged_epi && n_tail == 0);
-    if (n_tail > 0) a.n_major = 0;                     // K-split tiles keep the M-major numbering the reduce kernel uses
-    a.walk_div = a.n_major ? ntm : cdiv(a.N, BN);
-    walk_plan(a, BM, BN, ntm, cdiv(a.N, BN), smem);
+    plan_walk(a, BM, BN, ntm, ntn, smem, epi_store_fits(WM * WN, WTN / 32, NST * (BM + BN) * 128) && a.staged_epi, n_tail);
     a.tl = tl_take(WM * 100 + WN * 10 + (GLDS ? 1 : 0), a.n_main + n_tail * a.ksplit, NTHR, BM, BN, NST, a);
     report_launch(1, BM, BN, NST, AMODE, GLDS ? 1 : 0, a.n_main + n_tail * a.ksplit, a, smem, epi_variant(a, WM, WN, WTM, WTN, NST * (BM + BN) * 128), WM, WN);
     hipLaunchKernelGGL(kern, dim3(a.n_main + n_tail * a.ksplit), dim3(NTHR), smem, stream, a);
@@ -1419,14 +1226,7 @@ int launch_cfg_amode(const IGemmArgs& a_in, hipStream_t stream) {
 
 template <int WM, int WN, int WTM, int WTN, bool GLDS, int NST = 2>
 int launch_cfg(const IGemmArgs& a, hipStream_t stream) {
-    switch (a.amode) {
-        case 0: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 0, NST>(a, stream);
-        case 1: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 1, NST>(a, stream);
-        case 2: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 2, NST>(a, stream);
-        case 3: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 3, NST>(a, stream);
-        case 4: return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, 4, NST>(a, stream);
-        default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
-    }
+    return with_amode(a, [&](auto am) { return launch_cfg_amode<WM, WN, WTM, WTN, GLDS, decltype(am)::value, NST>(a, stream); });
 }
 
 // 32-deep K-tiles (tile32_kernel): any activation map; whole tiles
@@ -1449,18 +1249,10 @@ int launch_tile32_amode(const IGemmArgs& a_in, hipStream_t stream) {
     }
     static int attr_smem = 0;
     auto kern = tile32_kernel<WM, WN, WTM, WTN, NST, WPE, AMODE>;
-    if (smem > attr_smem) {
-        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_smem = smem;
-    }
+    if (const int rc = lds_limit(reinterpret_cast<const void*>(kern), attr_smem, smem)) return rc;
     const int ntn = cdiv(a.N, BN);
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = g_staged_epi;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
-    a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
-    if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
-    a.walk_div = a.n_major ? ntm : ntn;
-    walk_plan(a, BM, BN, ntm, ntn, smem);
-    stats_decide(a, NTHR / 64 * 32 * (WTN * 2 + 16) <= NST * (BM + BN) * 64 && a.staged_epi);
+    plan_walk(a, BM, BN, ntm, ntn, smem, epi_store_fits(WM * WN, WTN / 32, NST * (BM + BN) * 64) && a.staged_epi);
     a.tl = tl_take(3200 + WM * 100 + WN * 10, a.n_main, NTHR, BM, BN, NST, a);
     report_launch(2, BM, BN, NST, AMODE, 1, a.n_main, a, smem, epi_variant(a, WM, WN, WTM, WTN, NST * (BM + BN) * 64), WM, WN);
     hipLaunchKernelGGL(kern, dim3(a.n_main), dim3(NTHR), smem, stream, a);
@@ -1469,23 +1261,17 @@ int launch_tile32_amode(const IGemmArgs& a_in, hipStream_t stream) {
 }
 template <int WM, int WN, int WTM, int WTN, int NST, int WPE>
 int launch_tile32(const IGemmArgs& a, hipStream_t stream) {
-    switch (a.amode) {
-        case 0: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 0>(a, stream);
-        case 1: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 1>(a, stream);
-        case 2: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 2>(a, stream);
-        case 3: return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 3>(a, stream);
+    return with_amode(a, [&](auto am) {
+        constexpr int AMODE = decltype(am)::value;
         // (the 64 x 160 wave tiles - configs 20 / 27 - sit at 256 VGPRs and would spill with the phase maps: the 2x2 phase form is not
         //  instantiated for them; the 256 x 320 tile of igemm_kernel runs instead and the candidate reports that it did not run)
-        case 4: if constexpr (WTN == 160) { g_last_hint_applied = 0; return launch_cfg_amode<4, 2, 64, 160, true, 4, 2>(a, stream); }
-                else return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, 4>(a, stream);
-        default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
-    }
+        if constexpr (AMODE == 4 && WTN == 160) { g_last_hint_applied = 0; return launch_cfg_amode<4, 2, 64, 160, true, 4, 2>(a, stream); }
+        else return launch_tile32_amode<WM, WN, WTM, WTN, NST, WPE, AMODE>(a, stream);
+    });
 }
 
 }  // namespace
 
-// forced tile config for tests / tuning: 0 = heuristic; 1..8, 10 tile shapes; +20 (21..23) = register-staged
-// variant of the same tile (the LDS-DMA variant is the default)
 // 128 x 160 tile on 8 waves of 16x16x32 MFMAs (igemm16_kernel): whole tiles, plain-store epilogue
 static int g_mf16_heads = 1;           // 1: EPI_HEADS launches may use the tile too (head-major epilogue for the 16 x 16 layout; first run
                                        // on hardware in round 3: Q projection M = 4096 x N = 1280 432 -> 557 TF/s in situ)
@@ -1505,18 +1291,10 @@ int launch_mf16_amode(const IGemmArgs& a_in, hipStream_t stream) {
     if (smem > 160 * 1024) { g_last_hint_applied = 0; return launch_cfg_amode<4, 1, 32, 160, true, AMODE, 2>(a_in, stream); }   // (feature maps under 8 x 8: see launch_cfg_amode)
     static int attr_smem = 0;
     auto kern = igemm16_kernel<AMODE, NST>;
-    if (smem > attr_smem) {
-        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_smem = smem;
-    }
+    if (const int rc = lds_limit(reinterpret_cast<const void*>(kern), attr_smem, smem)) return rc;
     const int ntn = a.N / 160;
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = 1;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
-    a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
-    if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
-    a.walk_div = a.n_major ? ntm : ntn;
-    walk_plan(a, 128, 160, ntm, ntn, smem);
-    stats_decide(a, true);
+    plan_walk(a, 128, 160, ntm, ntn, smem, true);
     a.tl = tl_take(16, a.n_main, 512, 128, 160, NST, a);
     report_launch(3, 128, 160, NST, AMODE, 1, a.n_main, a, smem, epi_variant_staged_only(a), 4, 2);
     hipLaunchKernelGGL(kern, dim3(a.n_main), dim3(512), smem, stream, a);
@@ -1525,14 +1303,7 @@ int launch_mf16_amode(const IGemmArgs& a_in, hipStream_t stream) {
 }
 template <int NST>
 int launch_mf16(const IGemmArgs& a, hipStream_t stream) {
-    switch (a.amode) {
-        case 0: return launch_mf16_amode<0, NST>(a, stream);
-        case 1: return launch_mf16_amode<1, NST>(a, stream);
-        case 2: return launch_mf16_amode<2, NST>(a, stream);
-        case 3: return launch_mf16_amode<3, NST>(a, stream);
-        case 4: return launch_mf16_amode<4, NST>(a, stream);
-        default: cfgpp_set_error("igemm: bad amode %d", a.amode); return -2;
-    }
+    return with_amode(a, [&](auto am) { return launch_mf16_amode<decltype(am)::value, NST>(a, stream); });
 }
 
 // one wave per SIMD (big4_kernel.hip): 256 x 256 / 128 x 320 / 128 x 256 on four waves; whole tiles, staged epilogues
@@ -1549,12 +1320,7 @@ static int launch_big4(int cfg, const IGemmArgs& a_in, hipStream_t stream) {
     const int smem = big4_smem(cfg, a);
     const int ntm = cdiv(a.M, BM), ntn = cdiv(a.N, BN);
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = 1;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = a_bytes_of(a);
-    a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
-    if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
-    a.walk_div = a.n_major ? ntm : ntn;
-    walk_plan(a, BM, BN, ntm, ntn, smem);
-    stats_decide(a, true);
+    plan_walk(a, BM, BN, ntm, ntn, smem, true);
     a.tl = tl_take(4000 + cfg, a.n_main, 256, BM, BN, 2, a);
     report_launch(4, BM, BN, 2, a.amode, 1, a.n_main, a, smem, epi_variant_staged_only(a), 2, 2);
     return big4_run(cfg, a, a.n_main, smem, stream);
@@ -1567,12 +1333,7 @@ static int launch_big4p(const IGemmArgs& a_in, hipStream_t stream) {
     const int pb = big4_par_bytes(256, 0), smem = big4p_smem(pb);
     const int ntm = cdiv(a.M, 256), ntn = cdiv(a.N, 256);
     a.n_main = ntm * ntn; a.ksplit = 1; a.ws = nullptr; a.staged_epi = 1; a.tl = nullptr;
-    const double w_bytes = 2.0 * a.N * a.K, a_bytes = 2.0 * a.M * a.C0;
-    a.n_major = (g_n_major == 1 || (g_n_major < 0 && w_bytes > 1.5 * a_bytes && ntn >= 8)) ? 1 : 0;
-    if (g_n_major < 0 && a.walk_hint) a.n_major = a.walk_hint == 2 ? 1 : 0;
-    a.walk_div = a.n_major ? ntm : ntn;
-    walk_plan(a, 256, 256, ntm, ntn, smem);
-    stats_decide(a, true);
+    plan_walk(a, 256, 256, ntm, ntn, smem, true);      // (amode 0, one source - big4p_supports: the activation bytes are 2 M C0)
     report_launch(5, 256, 256, 2, 0, 1, a.n_main < 256 ? a.n_main : 256, a, smem, epi_variant_staged_only(a), 2, 4);
     return big4p_run(a, a.n_main < 256 ? a.n_main : 256, smem, pb, stream);
 }

@@ -409,7 +409,7 @@ def device_buffers(p: Problem):
 
 
 def im2col(p: Problem, ashift=None):
-    """[rows, K] fp32: the kernels' gather (igemm_kernel.hip load_tile) over device_buffers(p).src, K-tile by K-tile"""
+    """[rows, K] fp32: the kernels' gather (igemm_device.h a_row_map / a_gather / a_gather_pix) over device_buffers(p).src, K-tile by K-tile"""
     d = device_buffers(p)
     ashift = p.ashift if ashift is None else ashift
     flat = [s.reshape(-1, s.shape[-1]).astype(np.float32) for s in d.src]
