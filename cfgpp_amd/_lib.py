@@ -92,6 +92,11 @@ LONG_PROMPT_PROTOTYPES = {
     "cfgpp_unet_set_max_tokens": (_I, [_P, _I]),
 }
 
+# the FreeU extension header (include/cfgpp_freeu.h)
+FREEU_PROTOTYPES = {
+    "cfgpp_unet_set_freeu": (_I, [_P, _F, _F, _F, _F, _I]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_softmax_rows": (_I, [_P, _L, _I, _P]),
@@ -167,6 +172,8 @@ DEBUG_PROTOTYPES = {
     "cfgpp_groupnorm_last_launch": (None, [C.POINTER(C.c_int)]),
     "cfgpp_layernorm_last_launch": (None, [C.POINTER(C.c_int)]),
     "cfgpp_softmax_last_launch": (None, [C.POINTER(C.c_int)]),
+    "cfgpp_op_freeu": (_I, [_P, _I, _P, _I, _I, _I, _I, _F, _F, _P]),
+    "cfgpp_freeu_last_launch": (None, [C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -188,7 +195,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

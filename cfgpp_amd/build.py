@@ -26,6 +26,7 @@ SOURCES = [
     ("attn_kernel.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),   # scores are consumed by VALU: keep MFMA results in VGPRs
     ("controlnet_kernels.hip", ["-ffp-contract=off"]),   # the residual add is torch's fp16 `s + r * scale` bit for bit
     ("lora_kernels.hip", []),
+    ("freeu_kernel.hip", []),
     ("unet.hip", []),
     ("vae.hip", []),
     ("text.hip", []),

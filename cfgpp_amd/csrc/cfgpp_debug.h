@@ -130,6 +130,18 @@ int cfgpp_op_residual_nchw(const void* src, float* out, int rows, int H, int W, 
  * dense fp32 NCHW buffer out [rows][C][H][W].  Returns the number of residuals when out is NULL. */
 int cfgpp_controlnet_residual(cfgpp_unet* cn, int i, float scale, float* out, int rows, int* hwc_out, void* stream);
 
+/* FreeU on one (hidden, skip) pair as the UNet's plan runs it (include/cfgpp_freeu.h; csrc/freeu_kernel.hip), in place on halo-padded
+ * NHWC fp16 tensors [rows][H+2][W+2][C_h] / [..][C_s], ONE launch: hidden[:, :C_h / 2] = fp16(float(h) * b); skip = fp16(v + (s - 1) /
+ * (H W) * low(v)), low = the four frequencies {-1, 0} x {-1, 0} of the plane as fp32 sums against host-made fp32 twiddles.  Only
+ * interiors are read and written.  Either pointer may be NULL: that half of the job is not run.  Refused by name, nothing
+ * launched: H or W < 2 (or > 1024), C_h / 2 or C_s not a multiple of 8, non-finite b / s, both pointers NULL.  (The twiddle table of
+ * a plane size is uploaded synchronously on its first use: test hook.) */
+int cfgpp_op_freeu(void* hidden, int C_h, void* skip, int C_s, int rows, int H, int W, float b, float s, void* stream);
+/* test hook: what the last FreeU launch (cfgpp_op_freeu or a forward's) issued, a host-side record zeroed at entry (a refused call
+ * reports zeros): out5 = {path (0 nothing launched, 1 skip slab resident in LDS, 2 two-phase: planes over 4096 pixels are re-read
+ * from memory, 3 hidden half only), channels per skip slab, skip workgroups, hidden workgroups, dynamic LDS bytes} */
+void cfgpp_freeu_last_launch(int* out5);
+
 /* the CURRENT weight of matrix parameter `key` (base, or base + the adapters merged by cfgpp_unet_lora), read back from the
  * repacked device layout and un-repacked to checkpoint order: host_fp16_out holds [O][I][kh][kw] / [O][I] fp16.  Same keys and
  * refusals as cfgpp_unet_lora.  Synchronises the device. */

@@ -15,6 +15,7 @@
 #include "../../include/cfgpp.h"
 #include "../../include/cfgpp_ip_adapter.h"
 #include "../../include/cfgpp_long_prompt.h"
+#include "../../include/cfgpp_freeu.h"
 #include "cfgpp_debug.h"
 #include "igemm.h"
 
@@ -74,12 +75,15 @@ struct EngineBase {
     std::vector<std::string> plan_desc;
     // Shared CFG prefix (unet.hip): 1 = the op's inputs are the same for batch rows r and r + rows / 2 of a CFG call, so a call
     // that shares runs it on the leading rows / 2 rows only; 2 = the fan-out copy that ends the prefix (runs only in such a call)
+    // 3 = a FreeU edit (unet.hip): part of a call only while FreeU is on, so the off state walks, times and counts the plain plan
     std::vector<char> plan_share;
+    bool freeu_on = false;
     // batch rows op i of `plan` runs at in a call at `rows`: THE one place that decides it - every walk over `plan` asks here.
     // 0 = the op is not part of this call.
     int rows_for(size_t i, int rows, bool shared) const {
         const int m = i < plan_share.size() ? plan_share[i] : 0;
         if (m == 0) return rows;
+        if (m == 3) return freeu_on ? rows : 0;
         return shared ? rows / 2 : (m == 1 ? rows : 0);
     }
     void tag(int kind, double macs, const std::string& desc = "") {

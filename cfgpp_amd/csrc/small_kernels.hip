@@ -114,6 +114,7 @@ conv_out_kernel(const half_t* __restrict__ x, TOUT* __restrict__ out, const half
             x + ((long)(r * (H + 2) + y + 1 + dy) * (W + 2) + xq + 1 + dx) * C + cc);
 #pragma unroll
         for (int o = 0; o < CO; ++o) {
+            if (o >= cout_real) continue;       // w holds cout_real outputs: a 3-output call on the 4-wide instance must not read a 4th
             const half8_t wv = *reinterpret_cast<const half8_t*>(w + ((long)o * 9 + tap) * C + cc);
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc[o] += (float)xv[k] * (float)wv[k];
@@ -183,6 +184,7 @@ conv_out_tile_kernel(const half_t* __restrict__ x, TOUT* __restrict__ out, const
                 const half8_t xv = *reinterpret_cast<const half8_t*>(px + ch * 16);
 #pragma unroll
                 for (int o = 0; o < CO; ++o) {
+                    if (o >= cout_real) continue;       // (a 3-output fp16 call runs the 4-wide instance: w has no 4th output)
                     const half8_t wv = *reinterpret_cast<const half8_t*>(w + ((long)o * 9 + tap) * C + cb + ch * 8);      // wave-uniform: scalar loads
 #pragma unroll
                     for (int k = 0; k < 4; ++k)

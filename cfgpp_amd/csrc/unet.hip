@@ -10,6 +10,7 @@
 // launch plan (vector of closures) over preallocated, shape-keyed activation
 // buffers in halo-padded NHWC fp16 - no allocation, no host sync, one stream.
 #include "engine_base.h"
+#include "freeu.h"
 
 struct cfgpp_unet : EngineBase {
     cfgpp_unet_config cfg;
@@ -28,7 +29,8 @@ struct cfgpp_unet : EngineBase {
     hipStream_t cap_stream = nullptr;
     struct GraphKey { const void* z; void* z0t; void* eps; const void* euc; const void* ec; int z_half, z_rows, rows, tw, rn; float lam; long n; int tuned_serial; int cond_rows;
                       int ip_active = 0, ip_n_img = 0; unsigned ip_scale_bits = 0;         // the adapter state the captured launches baked in
-                      int ctx_tokens = 77; };       // the text context's token count: the captured cross-attention launches bake in nk, the kernel and its LDS size
+                      int ctx_tokens = 77;          // the text context's token count: the captured cross-attention launches bake in nk, the kernel and its LDS size
+                      int freeu_on = 0; unsigned freeu_bits[4] = {0, 0, 0, 0}; };     // FreeU state: the captured edits bake in s / b (off: no such launches)
     struct Graph { GraphKey key; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<Graph> graphs;              // most recently used last; at most 4 (an invert + edit job alternates between two)
     int tuned_serial = 0;                   // bumps whenever the pins of the current batch change (a graph bakes the tiles it captured)
@@ -84,6 +86,11 @@ struct cfgpp_unet : EngineBase {
     std::vector<Tensor> ctrl_dst;
     cfgpp_unet* ctrl = nullptr; float ctrl_scale = 0.f;
     CnAddEntry* d_ctrl_tab = nullptr; long ctrl_max_n8 = 0;
+
+    // ---- FreeU (cfgpp_unet_set_freeu; EngineBase::freeu_on): {s, b} of up_blocks.0 / up_blocks.1 and the twiddle table of each
+    // block's plane size (freeu_twiddles, built by finalize: the setter allocates nothing)
+    float freeu_s[2] = {1.f, 1.f}, freeu_b[2] = {1.f, 1.f};
+    float* d_freeu_tw[2] = {nullptr, nullptr};
 
     // ---- IP-Adapter (cfgpp_unet_ip_load / cfgpp_unet_image_context).  Every cross-attention block keeps its text K / V^T in
     // key slots [0, 77) of ck / cvt (ck_pad = 128 slots); the image tokens' K / V^T go into slots [96, 96 + n_img) of the same
@@ -732,6 +739,32 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         const std::string p = "up_blocks." + std::to_string(i);
         for (int j = 0; j < c.layers_per_block + 1; ++j) {
             Tensor skip = skips.back(); skips.pop_back();
+            if (i < 2) {
+                // FreeU (cfgpp_unet_set_freeu): x[:, :C / 2] *= b_i and the low-pass of `skip` scaled by s_i, IN PLACE, before the
+                // resnet that concatenates the two.  In place is safe: x is read only by this resblock's GroupNorm and 1x1
+                // shortcut and released right after it; `skip` is read only there too - the one skip the mid block also reads (its
+                // input) was read before the up path starts; the ControlNet residual add precedes the up path (diffusers adds the
+                // residuals to the skips first, then runs the up blocks); tune_plan and cfgpp_unet_profile re-run WHOLE forwards,
+                // which write both tensors again.  The statistics their producers left (Tensor::gst) describe the unedited values:
+                // where a tensor really changes (scale != 1) its flag is cleared, as the residual add does, and the GroupNorm
+                // takes its own.  plan_share 3: the op is part of a call only while FreeU is on (EngineBase::rows_for).
+                if (!u->d_freeu_tw[i]) {
+                    std::vector<float> tw((size_t)2 * x.H + 2 * x.W);
+                    freeu_twiddles(x.H, x.W, tw.data());
+                    u->d_freeu_tw[i] = B.upload(tw);
+                }
+                cfgpp_unet* uu = u;
+                const Tensor hx = x, sk = skip; const float* tw = u->d_freeu_tw[i]; const int blk = i;
+                u->plan.push_back([uu, hx, sk, tw, blk](hipStream_t s, int rows) {
+                    if (rows <= 0 || !uu->freeu_on) return 0;
+                    const float fb = uu->freeu_b[blk], fs = uu->freeu_s[blk];
+                    if (fb != 1.f && hx.gst_ok) *hx.gst_ok = 0;
+                    if (fs != 1.f && sk.gst_ok) *sk.gst_ok = 0;
+                    return freeu_launch(hx.p, hx.C, sk.p, sk.C, rows, hx.H, hx.W, fb, fs, tw, s);
+                });
+                u->tag(3, 0.0, "freeu " + p + ".resnets." + std::to_string(j));
+                u->plan_share.resize(u->plan.size(), 0); u->plan_share.back() = 3;
+            }
             Tensor y = resblock(p + ".resnets." + std::to_string(j), x, &skip, co);
             u->rel(x); u->rel(skip);
             if (c.level_has_attn[lvl]) {
@@ -799,6 +832,21 @@ int cfgpp_unet_set_max_tokens(cfgpp_unet* u, int max_tokens) {
     CFGPP_REQUIRE(max_tokens == 77 || max_tokens == 154 || max_tokens == 231 || max_tokens == 308,
                   "set_max_tokens: max_tokens=%d (77, 154, 231 or 308)", max_tokens);
     u->max_tokens = max_tokens;
+    return 0;
+}
+
+// diffusers UNet2DConditionModel.enable_freeu / disable_freeu; the edits themselves are the plan ops in front of the resnets of
+// up_blocks.0 / up_blocks.1 (finalize).  Host state only: the next forward reads it, a graph capture bakes it in (GraphKey).
+int cfgpp_unet_set_freeu(cfgpp_unet* u, float s1, float s2, float b1, float b2, int enable) {
+    CFGPP_REQUIRE(u && u->finalized, "set_freeu: the engine is not finalized");
+    CFGPP_REQUIRE(!u->control, "set_freeu: a ControlNet-mode engine (out_channels = 0) has no up path: FreeU applies to the UNet it is attached to");
+    if (!enable) { u->freeu_on = false; return 0; }
+    CFGPP_REQUIRE(std::isfinite(s1) && std::isfinite(s2) && std::isfinite(b1) && std::isfinite(b2),
+                  "set_freeu: non-finite value (s1=%f s2=%f b1=%f b2=%f)", (double)s1, (double)s2, (double)b1, (double)b2);
+    const int hmin = u->cfg.sample_h >> (u->cfg.num_levels - 1), wmin = u->cfg.sample_w >> (u->cfg.num_levels - 1);
+    CFGPP_REQUIRE(hmin >= 2 && wmin >= 2, "set_freeu: up_blocks.0 runs on %d x %d planes (the low-pass needs at least 2 x 2)", hmin, wmin);
+    u->freeu_s[0] = s1; u->freeu_s[1] = s2; u->freeu_b[0] = b1; u->freeu_b[1] = b2;
+    u->freeu_on = true;
     return 0;
 }
 
@@ -1101,11 +1149,17 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
     cfgpp_unet::GraphKey want{z, z0t, eps, eps_uc, eps_c, z_is_half, z_rows, rows, tweedie_uc, renoise_uc, lam, n, 0, u->cond_rows};
     want.ip_active = u->ip_active ? 1 : 0; want.ip_n_img = u->ip_n_img; std::memcpy(&want.ip_scale_bits, &u->ip_scale, sizeof(float));
     want.ctx_tokens = u->ctx_tokens;
+    want.freeu_on = u->freeu_on ? 1 : 0;
+    if (u->freeu_on) {
+        const float f[4] = {u->freeu_s[0], u->freeu_s[1], u->freeu_b[0], u->freeu_b[1]};
+        std::memcpy(want.freeu_bits, f, sizeof(f));
+    }
     auto same = [&](const cfgpp_unet::GraphKey& k) {
         return k.z == want.z && k.z0t == want.z0t && k.eps == want.eps && k.euc == want.euc && k.ec == want.ec && k.z_half == want.z_half &&
                k.z_rows == want.z_rows && k.rows == want.rows && k.tw == want.tw && k.rn == want.rn && k.lam == want.lam && k.n == want.n &&
                k.tuned_serial == u->tuned_serial && k.cond_rows == want.cond_rows && k.ip_active == want.ip_active &&
-               k.ip_n_img == want.ip_n_img && k.ip_scale_bits == want.ip_scale_bits && k.ctx_tokens == want.ctx_tokens;
+               k.ip_n_img == want.ip_n_img && k.ip_scale_bits == want.ip_scale_bits && k.ctx_tokens == want.ctx_tokens &&
+               k.freeu_on == want.freeu_on && std::memcmp(k.freeu_bits, want.freeu_bits, sizeof(want.freeu_bits)) == 0;
     };
     int hit = -1;
     for (size_t i = 0; i < u->graphs.size(); ++i) if (same(u->graphs[i].key)) hit = (int)i;

@@ -191,6 +191,7 @@ class HipUNet:
         self.max_tokens = 77
         if int(max_tokens) != 77:
             self.set_max_tokens(max_tokens)
+        self.freeu = None                            # (s1, s2, b1, b2) while FreeU is on (set_freeu)
         self.latent_channels = cfg.out_channels      # z carries these; an inpaint UNet's other inputs come from image_condition
         self.cond_channels = cfg.in_channels - cfg.out_channels
 
@@ -364,6 +365,16 @@ class HipUNet:
         check(self.lib.cfgpp_unet_image_context(self._h, e.data_ptr(), int(e.shape[0]), int(e.shape[1]), float(scale), stream),
               "cfgpp_unet_image_context")
         self._keep["ip_embeds"] = e
+
+    def set_freeu(self, spec):
+        """diffusers' ``enable_freeu(s1, s2, b1, b2)`` (``spec`` = that tuple, or a mapping with those keys) / ``disable_freeu()``
+        (None) on the finalized engine (include/cfgpp_freeu.h: cfgpp_unet_set_freeu).  Host state only; the next forward sees it."""
+        from .freeu import parse_freeu
+        v = parse_freeu(spec)
+        s1, s2, b1, b2 = v if v is not None else (1.0, 1.0, 1.0, 1.0)
+        check(self.lib.cfgpp_unet_set_freeu(self._h, s1, s2, b1, b2, 0 if v is None else 1), "cfgpp_unet_set_freeu")
+        self.freeu = v
+        return self
 
     def attach_control(self, cn, scale: float):
         """attach ControlNet ``cn`` (a finalized :class:`cfgpp_amd.controlnet.HipControlNet`; None detaches) with

@@ -169,6 +169,18 @@ class HipEngine:
             raise CfgppError(f"ip_adapter_image_embeds: embed_dim {int(embeds.shape[-1])}, the adapter takes {self.ip_adapter.embed_dim}")
         self.unet.set_image_context(assemble_embeds(embeds, negative, self.B), float(scale))
 
+    # -- FreeU -----------------------------------------------------------------------
+    def set_freeu(self, spec):
+        """``(s1, s2, b1, b2)`` (diffusers ``enable_freeu``; a mapping with those keys works too) or None (off: the plain engine, bit
+        for bit and launch for launch).  A property of the UNet: an attached ControlNet is not touched.  Weights, tile pins and the
+        conditioning stay; a captured graph of another FreeU state is never replayed (include/cfgpp_freeu.h)."""
+        self.unet.set_freeu(spec)
+        return self
+
+    @property
+    def freeu(self):
+        return self.unet.freeu
+
     # -- LoRA ------------------------------------------------------------------------
     def set_lora(self, adapters, ignore_text_encoder: bool = False):
         """``adapters``: list of ``(parsed | safetensors path | state dict, scale)``; ``[]`` restores the base weights.  One merge

@@ -150,6 +150,11 @@ class StableDiffusion:
         if kwargs.get("ip_adapter") is not None:
             self.set_ip_adapter(kwargs["ip_adapter"])
 
+        # FreeU (diffusers enable_freeu): (s1, s2, b1, b2) or a mapping with those keys; a property of the UNet, so every solver
+        # takes it - inversion and edit included - and a ControlNet is not affected.  None / absent: the plain engine.
+        if kwargs.get("freeu") is not None:
+            self.set_freeu(kwargs["freeu"])
+
         if kwargs.get("lora"):              # [(safetensors path | state dict | parsed, scale), ...] merged into the UNet on the device
             self.set_lora(kwargs["lora"], ignore_text_encoder=kwargs.get("lora_ignore_text_encoder", False))
 
@@ -193,6 +198,21 @@ class StableDiffusion:
         cur = eng.lora_adapters
         if any(float(s) != float(scale) for _, s in cur):
             eng.set_lora([(p, float(scale)) for p, _ in cur])
+
+    # ------------------------------------------------------------------ FreeU
+    def set_freeu(self, spec):
+        """``(s1, s2, b1, b2)`` | mapping with those keys | None (off) for the engine's UNet (cfgpp_amd/freeu.py); takes effect
+        with the next prediction"""
+        from .freeu import parse_freeu
+        vals = parse_freeu(spec)            # a bad spec is refused here, by name, before anything reaches the engine
+        if not hasattr(self.engine, "set_freeu"):
+            raise ValueError(f"freeu=...: the engine {type(self.engine).__name__} has no FreeU")
+        self.engine.set_freeu(vals)
+
+    @property
+    def freeu(self):
+        """the (s1, s2, b1, b2) in force, or None"""
+        return getattr(self.engine, "freeu", None)
 
     # ------------------------------------------------------------------ IP-Adapter
     def set_ip_adapter(self, spec):

@@ -48,6 +48,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--inpaint_unet", action="store_true", help="synthetic 9-channel inpaint UNet instead of the 4-channel one")
+    from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
+    add_cli_flag(ap)
     args = ap.parse_args(argv)
     if args.mask_path is None:
         ap.error("--mask_path is required")
@@ -80,6 +82,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         from cfgpp_amd.lora import parse_cli
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
+    cli_kwargs(args, kw)
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

@@ -49,6 +49,8 @@ def main(argv=None, solver_kwargs=None) -> None:
                          "77 x K text tokens (cfgpp_amd/prompt.py); 1 (default): prompts cut at 75 ids, brackets literal")
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
+    from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
+    add_cli_flag(ap)
     args = ap.parse_args(argv)
 
     from cfgpp_amd.callback_util import save_image
@@ -74,6 +76,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         from cfgpp_amd.lora import parse_cli
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
+    cli_kwargs(args, kw)
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

@@ -62,6 +62,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--ip_adapter_dir", default=None, help="folder that holds the CLIP image tower (image_encoder/)")
     ap.add_argument("--ip_embeds", default=None, metavar="FILE.npy", help="precomputed CLIP image embeds [1 or batch, embed_dim]")
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
+    from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
+    add_cli_flag(ap)
     args = ap.parse_args(argv)
 
     from cfgpp_amd.callback_util import ComposeCallback, save_image
@@ -88,6 +90,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
     ip_kwargs = _ip_kwargs(args, kw)
+    cli_kwargs(args, kw)
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

@@ -55,6 +55,8 @@ def main(argv=None, solver_kwargs=None) -> int:
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--no_draw", action="store_true", help="skip the per-step draw_noisy / draw_tweedie decodes")
+    from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
+    add_cli_flag(ap)
     args = ap.parse_args(argv)
 
     from cfgpp_amd import dist
@@ -84,6 +86,7 @@ def main(argv=None, solver_kwargs=None) -> int:
         from cfgpp_amd.lora import parse_cli
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
+    cli_kwargs(args, kw)
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})
