@@ -97,6 +97,13 @@ FREEU_PROTOTYPES = {
     "cfgpp_unet_set_freeu": (_I, [_P, _F, _F, _F, _F, _I]),
 }
 
+# the v-prediction extension header (include/cfgpp_vpred.h)
+VPRED_PROTOTYPES = {
+    "cfgpp_step_ddim_v": (_I, [_P, _P, _P, _P, _I, _F, C.POINTER(C.c_float), _I, _I, _P, _L, _L, _P]),
+    "cfgpp_v_to_eps": (_I, [_P, _P, _P, _P, _P, _I, _F, _F, _L, _P]),
+    "cfgpp_cfg_rescale": (_I, [_P, _P, _F, _F, _P, _I, _L, _P]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_softmax_rows": (_I, [_P, _L, _I, _P]),
@@ -195,7 +202,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

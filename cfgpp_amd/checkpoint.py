@@ -6,6 +6,11 @@ copy of such a checkpoint (no hub access here) the same components map onto this
 
     <dir>/unet/diffusion_pytorch_model.safetensors          -> unet_weights=   (HIP UNet engine)
     <dir>/unet/config.json, "in_channels": 9                -> unet_config=    (SD15_INPAINT / SDXL_INPAINT: an inpaint checkpoint)
+    <dir>/unet/config.json, cross_attention_dim / attention_head_dim / use_linear_projection / sample_size
+                                                            -> unet_config=    (SD21 / SD21_BASE: a Stable Diffusion 2.x UNet)
+    <dir>/scheduler/scheduler_config.json                   -> prediction_type= / zero_terminal_snr= / timestep_spacing=
+                                                               (only what differs from "epsilon" / false / "leading")
+    <dir>/tokenizer/special_tokens_map.json, pad_token      -> the text tower's padding ("!" for SD2.x)
     <dir>/vae/diffusion_pytorch_model.safetensors           -> vae_weights=    (HIP VAE engine; SD1.5 only)
     <dir>/vae_fp16_fix/diffusion_pytorch_model.safetensors  -> vae_weights=    (SDXL: the reference REPLACES the pipeline's VAE with
                                                                madebyollin/sdxl-vae-fp16-fix, latent_sdxl.py:44,396 - the stock
@@ -46,6 +51,49 @@ def _weights_in(folder, stem="diffusion_pytorch_model"):
     return _first(os.path.join(folder, stem + ".safetensors"), os.path.join(folder, stem + ".fp16.safetensors"))
 
 
+def _default_unet_config(sdxl: bool):
+    from .unet_config import SD15, SDXL
+    return SDXL if sdxl else SD15
+
+
+def unet_config_from_json(conf: dict, base):
+    """``base`` with the fields a diffusers ``unet/config.json`` may set differently inside one family - ``cross_attention_dim``,
+    ``attention_head_dim`` (an int or one entry per level: diffusers' name for the head COUNT), ``use_linear_projection``,
+    ``sample_size`` - or None when the file describes ``base`` itself.  A config that is one of the named SD2.x ones is returned as
+    that object (``SD21``, ``SD21_BASE``)."""
+    from dataclasses import replace
+    from .unet_config import SD21, SD21_BASE
+    L = base.num_levels
+    heads = conf.get("attention_head_dim")
+    if heads is None:
+        heads = base.num_heads
+    heads = tuple(int(h) for h in heads) if isinstance(heads, (list, tuple)) else (int(heads),) * L
+    if len(heads) != L:
+        raise CfgppError(f"unet/config.json: attention_head_dim has {len(heads)} entries for {L} levels")
+    lin = conf.get("use_linear_projection")
+    lin = base.linear_projection if lin is None or bool(lin) == base.use_linear_projection else bool(lin)
+    cand = replace(base, num_heads=heads, cross_attention_dim=int(conf.get("cross_attention_dim") or base.cross_attention_dim),
+                   linear_projection=lin, sample_size=int(conf.get("sample_size") or base.sample_size))
+    if cand == base:
+        return None
+    for named in (SD21, SD21_BASE):
+        if replace(cand, name=named.name) == named:
+            return named
+    return replace(cand, name=base.name + "_custom")
+
+
+def _pad_token(path):
+    """the pad token of a ``special_tokens_map.json`` when it is not CLIP's default ``<|endoftext|>`` (None otherwise)"""
+    if not os.path.exists(path):
+        return None
+    import json
+    with open(path) as f:
+        tok = json.load(f).get("pad_token")
+    if isinstance(tok, dict):
+        tok = tok.get("content")
+    return tok if tok and tok != "<|endoftext|>" else None
+
+
 def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, text_tower: str = "") -> Tuple[Dict, List[str]]:
     """(kwargs for ``get_solver``, names of the components not found).  ``vae_dir``: a folder holding the VAE weights,
     overriding the default lookup (SD1.5: ``<dir>/vae``; SDXL: ``<dir>/vae_fp16_fix`` or ``<dir>/sdxl-vae-fp16-fix`` -
@@ -75,10 +123,31 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
     if os.path.exists(ucfg):            # an inpaint checkpoint's UNet takes 9 input channels (latent, mask, masked-image latent)
         import json
         with open(ucfg) as f:
-            cin = int(json.load(f).get("in_channels", 4))
+            uconf = json.load(f)
+        cin = int(uconf.get("in_channels", 4))
         if cin == 9:
             from .unet_config import SD15_INPAINT, SDXL_INPAINT
             kw["unet_config"] = SDXL_INPAINT if sdxl else SD15_INPAINT
+        shaped = unet_config_from_json(uconf, kw.get("unet_config") or _default_unet_config(sdxl))
+        if shaped is not None:          # an SD2.x UNet, or another head count / context width / projection kind than the family's
+            kw["unet_config"] = shaped
+    # what the UNet predicts and the schedule it was trained on: only what differs from the reference's models is passed on, so a
+    # plain SD1.5 / SDXL directory yields the keyword arguments it always did
+    scfg = os.path.join(d, "scheduler", "scheduler_config.json")
+    if os.path.exists(scfg):
+        import json
+        with open(scfg) as f:
+            sconf = json.load(f)
+        pt = sconf.get("prediction_type", "epsilon")
+        if pt != "epsilon":
+            kw["prediction_type"] = pt          # "v_prediction"; anything else is refused by the solver, by name
+        if sconf.get("rescale_betas_zero_snr"):
+            kw["zero_terminal_snr"] = True
+        if sconf.get("timestep_spacing") == "trailing":
+            kw["timestep_spacing"] = "trailing"
+    pad_token = _pad_token(os.path.join(d, "tokenizer", "special_tokens_map.json"))
+    if pad_token is not None:
+        kw["pad_token"] = pad_token             # SD2.x pads with "!" (the solvers ignore the key; the text tower below takes it)
     lora = _first(os.path.join(d, "pytorch_lora_weights.safetensors"), os.path.join(d, "lora.safetensors"))
     if lora:
         # a LoRA file next to the model (diffusers' save_lora_weights name, or lora.safetensors): merged into the UNet at scale 1
@@ -125,7 +194,7 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
         if t1 is not None and t2 is not None:
             kw["text_encoder"] = (t1, t2)
     else:
-        t1 = tower("text_encoder", "tokenizer", penultimate=False, with_projection=False)
+        t1 = tower("text_encoder", "tokenizer", penultimate=False, with_projection=False, **({} if pad_token is None else {"pad_token": pad_token}))
         if t1 is not None:
             kw["text_encoder"] = t1
     return kw, missing

@@ -78,6 +78,29 @@ def ddim_coeffs_pinned(sqrt4, eps_half: bool = True, semantics: str = "cpu", z_h
     return (_first(c1, eps_half, semantics), divisor(c2, semantics), _first(c3, z_half, semantics), _first(c4, eps_half, semantics))
 
 
+def ddim_v_coeffs_pinned(sqrt4, semantics: str = "cpu", z_half: bool = False, device_alpha=None):
+    """(a_z, s_v, a_v, s_z, c3, c4) for cfgpp_step_ddim_v (include/cfgpp_vpred.h) from the same pinned ``sqrt4`` =
+    (sqrt(1-a_tw), sqrt(a_tw), sqrt(a_rn), sqrt(1-a_rn)) that :func:`ddim_coeffs_pinned` takes:
+        z0t = a_z*z - s_v*A ; epsB = a_v*B + s_z*z ; z' = c3*z0t + c4*epsB,   a_z = a_v = sqrt(a_tw), s_v = s_z = sqrt(1-a_tw).
+    The six are separate because the scalar-first rule applies per product: s_v and a_v multiply the fp16 v and are pre-rounded to
+    fp16 under ``"cpu"``; a_z, s_z, c3 and c4 multiply the latent (or a value of its dtype) and are pre-rounded only when the
+    latent itself is fp16 (``z_half``).  There is no divisor.  ``device_alpha`` as in :func:`ddim_coeffs_pinned`: that level's
+    scalars are 0-dim DEVICE tensors and follow the ordinary-operand rule (the ``"cpu"`` rounding) on every backend."""
+    c1, c2, c3, c4 = (_s(v) for v in sqrt4)
+    tw = "cpu" if (semantics == "cuda" and device_alpha == "tw") else semantics
+    rn = "cpu" if (semantics == "cuda" and device_alpha == "rn") else semantics
+    return (_first(c2, z_half, tw), _first(c1, True, tw), _first(c2, True, tw), _first(c1, z_half, tw),
+            _first(c3, z_half, rn), _first(c4, z_half, rn))
+
+
+def v_to_eps_coeffs(sigma, semantics: str = "cpu"):
+    """(a, s) of cfgpp_v_to_eps at ``sigma``: a = 1/sqrt(sigma^2+1), s = sigma/sqrt(sigma^2+1) as 0-dim fp32 expressions, both
+    scalar-first products with an fp16 tensor."""
+    sig = _s(sigma)
+    den = (sig ** 2 + 1) ** 0.5
+    return _first(1.0 / den, True, semantics), _first(sig / den, True, semantics)
+
+
 def kdiff_input_scale_sd(sigma, semantics: str = "cpu") -> float:
     """divisor of ``x / (sigma**2 + 1)**0.5`` (latent_diffusion.py:229-230), as :func:`divisor` encodes it."""
     return divisor((_s(sigma) ** 2 + 1) ** 0.5, semantics)

@@ -142,6 +142,70 @@ def lincomb(out, x, y, z, a: float, b: float, mode: int):
 
 
 # ----------------------------------------------------------------------------
+# v-prediction (include/cfgpp_vpred.h)
+# ----------------------------------------------------------------------------
+def step_ddim_v(z: torch.Tensor, z0t_out: torch.Tensor, v_uc: torch.Tensor, v_c: torch.Tensor, lam: float, coef6,
+                tweedie_uc: bool, renoise_uc: bool, row_scale: Optional[torch.Tensor] = None):
+    """In-place generalised DDIM update of a v-prediction model (cfgpp_step_ddim_v): ``coef6`` = (a_z, s_v, a_v, s_z, c3, c4) from
+    ``coeffs.ddim_v_coeffs_pinned``; z / z0t_out both fp32 or both fp16, v fp16.  ``row_scale``: fp32 [B] from :func:`cfg_rescale`
+    (z is then [B, ...]), or None."""
+    lib = _lib.load()
+    for n, t in (("z", z), ("z0t_out", z0t_out), ("v_uc", v_uc), ("v_c", v_c)):
+        _require_cuda(t, n)
+    if z.dtype != z0t_out.dtype or z.dtype not in (torch.float16, torch.float32):
+        raise CfgppError("step_ddim_v: z and z0t_out must both be fp32 or both fp16")
+    if v_uc.dtype != torch.float16 or v_c.dtype != torch.float16:
+        raise CfgppError("step_ddim_v: v must be fp16")
+    if not (z.numel() == z0t_out.numel() == v_uc.numel() == v_c.numel()):
+        raise CfgppError("step_ddim_v: size mismatch")
+    if len(coef6) != 6:
+        raise CfgppError("step_ddim_v: coef6 = (a_z, s_v, a_v, s_z, c3, c4)")
+    row_elems = 0
+    if row_scale is not None:
+        _require_cuda(row_scale, "row_scale")
+        if row_scale.dtype != torch.float32 or row_scale.numel() != int(z.shape[0]):
+            raise CfgppError(f"step_ddim_v: row_scale must be fp32 [{int(z.shape[0])}]")
+        row_elems = z.numel() // int(z.shape[0])
+    arr = (C.c_float * 6)(*[float(v) for v in coef6])
+    check(lib.cfgpp_step_ddim_v(z.data_ptr(), z0t_out.data_ptr(), v_uc.data_ptr(), v_c.data_ptr(), 1 if z.dtype == torch.float16 else 0,
+                                float(lam), arr, int(bool(tweedie_uc)), int(bool(renoise_uc)), _ptr(row_scale), row_elems, z.numel(),
+                                _stream_ptr(z)), "cfgpp_step_ddim_v")
+
+
+def v_to_eps(eps_uc_out: torch.Tensor, eps_c_out: torch.Tensor, v_uc: torch.Tensor, v_c: torch.Tensor, x: torch.Tensor, a: float, s: float):
+    """eps = a*v + s*x for both CFG halves in one launch (cfgpp_v_to_eps), all fp16; the outputs may be the inputs."""
+    lib = _lib.load()
+    for n, t in (("eps_uc_out", eps_uc_out), ("eps_c_out", eps_c_out), ("v_uc", v_uc), ("v_c", v_c), ("x", x)):
+        _require_cuda(t, n)
+        if t.dtype != torch.float16:
+            raise CfgppError(f"v_to_eps: {n} must be fp16")
+        if t.numel() != x.numel():
+            raise CfgppError("v_to_eps: size mismatch")
+    check(lib.cfgpp_v_to_eps(eps_uc_out.data_ptr(), eps_c_out.data_ptr(), v_uc.data_ptr(), v_c.data_ptr(), x.data_ptr(), 1, float(a),
+                             float(s), x.numel(), _stream_ptr(x)), "cfgpp_v_to_eps")
+
+
+def cfg_rescale(v_uc: torch.Tensor, v_c: torch.Tensor, lam: float, phi: float, row_scale_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [B]: the per-sample factor of diffusers' ``rescale_noise_cfg`` (cfgpp_cfg_rescale); v_uc / v_c fp16 [B, ...]."""
+    lib = _lib.load()
+    for n, t in (("v_uc", v_uc), ("v_c", v_c)):
+        _require_cuda(t, n)
+        if t.dtype != torch.float16:
+            raise CfgppError(f"cfg_rescale: {n} must be fp16")
+    if v_uc.shape != v_c.shape or v_uc.dim() < 2:
+        raise CfgppError("cfg_rescale: v_uc / v_c must be [B, ...] of one shape")
+    B = int(v_uc.shape[0])
+    if row_scale_out is None:
+        row_scale_out = torch.empty((B,), dtype=torch.float32, device=v_uc.device)
+    _require_cuda(row_scale_out, "row_scale_out")
+    if row_scale_out.dtype != torch.float32 or row_scale_out.numel() != B:
+        raise CfgppError(f"cfg_rescale: row_scale_out must be fp32 [{B}]")
+    check(lib.cfgpp_cfg_rescale(v_uc.data_ptr(), v_c.data_ptr(), float(lam), float(phi), row_scale_out.data_ptr(), B, v_uc.numel() // B,
+                                _stream_ptr(v_uc)), "cfgpp_cfg_rescale")
+    return row_scale_out
+
+
+# ----------------------------------------------------------------------------
 # UNet engine
 # ----------------------------------------------------------------------------
 def unet_config_c(cfg: UNetConfig, H: int, W: int, max_rows: int, out_channels: Optional[int] = None) -> UNetConfigC:

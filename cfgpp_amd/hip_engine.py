@@ -250,6 +250,10 @@ class HipEngine:
     step_kdiff = staticmethod(E.step_kdiff)
     kdiff_denoise = staticmethod(E.kdiff_denoise)
     lincomb = staticmethod(E.lincomb)
+    # v-prediction (include/cfgpp_vpred.h)
+    step_ddim_v = staticmethod(E.step_ddim_v)
+    v_to_eps = staticmethod(E.v_to_eps)
+    cfg_rescale = staticmethod(E.cfg_rescale)
 
     def randn_like(self, x):
         """ancestral noise: device RNG, like the reference's torch.randn_like on the GPU"""

@@ -77,6 +77,7 @@ class _InpaintMixin:
 
     cfgpp = False
     controllable = False        # ControlNet on inpaint UNets is not supported: sample() refuses control_image
+    vpred_ok = False            # the masked update and the forward-noised source are epsilon arithmetic: v-prediction is refused
 
     @property
     def inpaint_unet(self) -> bool:

@@ -50,7 +50,11 @@ def controlled(sample):
 
     ``sample(..., ip_adapter_image_embeds=[1 or B, embed_dim] | ip_adapter_image=[1 or B, 3, H, W] in [0, 1],
     negative_ip_adapter_image_embeds=None, ip_adapter_scale=1.0)``: an image prompt for the solver's IP-Adapter
-    (``get_solver(..., ip_adapter=...)`` / ``set_ip_adapter``) for this call; the same solvers refuse these arguments."""
+    (``get_solver(..., ip_adapter=...)`` / ``set_ip_adapter``) for this call; the same solvers refuse these arguments.
+
+    ``sample(..., guidance_rescale=phi)``: diffusers' ``rescale_noise_cfg`` factor for this call, overriding
+    ``get_solver(..., guidance_rescale=)``; `ddim` / `ddim_cfg++` with ``prediction_type="v_prediction"`` only, refused by name
+    elsewhere."""
     @functools.wraps(sample)
     def run(self, *args, **kwargs):
         image = kwargs.pop("control_image", None)
@@ -64,6 +68,9 @@ def controlled(sample):
         lora_scale = kwargs.pop("lora_scale", None)
         if lora_scale is not None:          # shorthand: every adapter of the solver at this scale, from this job on
             self.set_lora_scale(lora_scale)
+        if "guidance_rescale" in kwargs:    # this job's rescale_noise_cfg factor, overriding get_solver(guidance_rescale=)
+            phi = kwargs.pop("guidance_rescale")
+            self._job_rescale = None if phi is None else self._check_guidance_rescale(phi)
         if image is not None and not self.controllable:
             raise ValueError(f"{type(self).__name__}.sample() does not take control_image: ControlNet conditioning is for the "
                              "text-to-image solvers (inversion, edit and inpaint solvers refuse it)")
@@ -72,6 +79,7 @@ def controlled(sample):
                 return sample(self, *args, **kwargs)
         finally:
             self._ip_job = None
+            self._job_rescale = None
     return run
 
 
@@ -112,8 +120,19 @@ class StableDiffusion:
             raise ValueError(f"ip_adapter=... together with max_prompt_chunks={self.max_prompt_chunks} is not supported: the IP-Adapter's "
                              "image tokens sit at key 96 of a 128-slot cross-attention buffer (max_prompt_chunks must be 1)")
 
+        # what the UNet predicts and on which schedule (DESIGN.md "v-prediction"): "epsilon" / "leading" / no rescaling are the
+        # reference's models, bit for bit
+        self.prediction_type = kwargs.get("prediction_type") or "epsilon"
+        zero_snr = bool(kwargs.get("zero_terminal_snr", False))
+        spacing = kwargs.get("timestep_spacing") or "leading"
+        if self.scheduler_kind == "lightning":      # its Euler scheduler has its own (trailing) timesteps, whatever a checkpoint's file says
+            spacing = "leading"
+        self._job_rescale = None
+        self._refuse_unsupported_prediction(zero_snr, spacing)
+        self.guidance_rescale = self._check_guidance_rescale(kwargs.get("guidance_rescale") or 0.0)
+
         # scheduler tables (host)
-        self.tables = SchedulerTables(solver_config.num_sampling, self.scheduler_kind)
+        self.tables = SchedulerTables(solver_config.num_sampling, self.scheduler_kind, zero_terminal_snr=zero_snr, timestep_spacing=spacing)
         self.scheduler = _SchedulerView(self.tables)
         self.total_alphas = self.tables.total_alphas
         self.sigmas = self.tables.sigmas
@@ -180,6 +199,61 @@ class StableDiffusion:
         return self.tables.alpha(t)
 
     controllable = True         # text-to-image: sample() takes control_image (see `controlled`)
+
+    # ------------------------------------------------------------------ v-prediction, zero terminal SNR, guidance rescale
+    solver_name = None          # the registry name (registry.py)
+    sigma_solver = False        # Karras-sigma (k-diffusion) loop: sigma_max of a zero-terminal-SNR schedule is infinite
+    vpred_ok = True             # False: the solver's update has no v form (inpaint blend)
+    rescale_ok = False          # True on `ddim` / `ddim_cfg++`: the text-to-image DDIM loops take guidance_rescale
+
+    def _name(self) -> str:
+        return f"solver '{self.solver_name or type(self).__name__}'"
+
+    def _refuse_unsupported_prediction(self, zero_snr: bool, spacing: str):
+        """every combination the v-prediction path does not cover is refused here, by name, before anything is built"""
+        pt = self.prediction_type
+        if pt not in ("epsilon", "v_prediction"):
+            raise ValueError(f"prediction_type={pt!r}: 'epsilon' or 'v_prediction' ('sample'-prediction models are not supported)")
+        if pt == "v_prediction" and self.scheduler_kind == "lightning":
+            raise ValueError(f"{self._name()}: prediction_type='v_prediction' is not supported by the *_lightning solvers")
+        if pt == "v_prediction" and not self.vpred_ok:
+            raise ValueError(f"{self._name()}: prediction_type='v_prediction' is not supported by the inpaint solvers")
+        if zero_snr and self.sigma_solver:
+            raise ValueError(f"{self._name()}: zero_terminal_snr=True is not supported by the Karras-sigma solvers (euler*, dpm++_2m*, "
+                             "dpm++_2s_a*): sigma_max is infinite")
+        if zero_snr and pt == "epsilon":
+            raise ValueError(f"{self._name()}: zero_terminal_snr=True needs prediction_type='v_prediction': the epsilon update divides by "
+                             "sqrt(alpha_T) = 0")
+
+    def _check_guidance_rescale(self, phi) -> float:
+        phi = float(phi)
+        if not 0.0 <= phi <= 1.0:
+            raise ValueError(f"guidance_rescale={phi}: 0 (off) .. 1")
+        if phi > 0.0 and self.prediction_type != "v_prediction":
+            raise ValueError(f"{self._name()}: guidance_rescale={phi} needs prediction_type='v_prediction' (not supported for epsilon models)")
+        if phi > 0.0 and not self.rescale_ok:
+            raise ValueError(f"{self._name()}: guidance_rescale={phi} is supported by 'ddim' and 'ddim_cfg++' only (inversion, edit and "
+                             "k-diffusion solvers refuse it)")
+        return phi
+
+    def _update_hook(self):
+        """the ``update=`` of ``_ddim_loop``: None (``_ddim_update``, epsilon) or the v-prediction update"""
+        return self._ddim_update_v if self.prediction_type == "v_prediction" else None
+
+    def _ddim_update_v(self, zt, z0t, v_uc, v_c, lam, sqrt4, tweedie_uc, renoise_uc, device_alpha=None, last=False):
+        """``_ddim_update`` for a v-prediction UNet: one cfgpp_step_ddim_v launch, after one cfgpp_cfg_rescale launch when
+        guidance_rescale > 0 (include/cfgpp_vpred.h)"""
+        co = K.ddim_v_coeffs_pinned(sqrt4, semantics=self.scalar_semantics, z_half=(zt.dtype == torch.float16), device_alpha=device_alpha)
+        phi = self.guidance_rescale if self._job_rescale is None else self._job_rescale
+        row_scale = self.engine.cfg_rescale(v_uc, v_c, lam, phi) if phi > 0.0 else None
+        self.engine.step_ddim_v(zt, z0t, v_uc, v_c, lam, co, tweedie_uc, renoise_uc, row_scale)
+
+    def _eps_from_v(self, noise_uc, noise_c, xc, sigma):
+        """k-diffusion loops: the UNet's v at the scaled input ``xc`` -> eps, in place (one cfgpp_v_to_eps launch); a no-op for
+        epsilon models"""
+        if self.prediction_type == "v_prediction":
+            a, s = K.v_to_eps_coeffs(sigma, self.scalar_semantics)
+            self.engine.v_to_eps(noise_uc, noise_c, noise_uc, noise_c, xc, a, s)
 
     # ------------------------------------------------------------------ LoRA
     def set_lora(self, adapters, ignore_text_encoder: bool = False):
@@ -382,6 +456,8 @@ class StableDiffusion:
         ``final_alpha_cumprod.to(device)``: the renoising alpha ("rn") forward, the x0-estimate alpha ("tw") in an inversion.
         ``wrap`` (quirk Q3): SDXL's `ddim` loops index the shifted table unguarded and never take the final alpha."""
         sqrt4 = self.tables.ddim_sqrt_coeffs(t, wrap=wrap, inversion=inversion)
+        if self.tables.timestep_spacing == "trailing":      # diffusers' indexing: abar[0] past the start is a table entry like the rest
+            return sqrt4, None
         final = not wrap and int(t) - self.tables.skip < 0
         return sqrt4, (("tw" if inversion else "rn") if final else None)
 
@@ -389,8 +465,9 @@ class StableDiffusion:
         """The DDIM loop with callback_fn None as hipGraph replays of ONE captured step (UNet + fused update; include/cfgpp.h:
         cfgpp_sample_graph_ddim) when the engine offers it ($CFGPP_GRAPH=1 on the HIP engine): the per-step scalars - exactly
         what the eager loop hands to ``predict`` / ``step_ddim`` - are computed up front.
-        Returns (z0t, zt) or None when the eager loop has to run (mock engine, switch off)."""
-        if not getattr(self.engine, "graph_enabled", False):
+        Returns (z0t, zt) or None when the eager loop has to run (mock engine, switch off, a v-prediction model: the captured
+        step is the epsilon update)."""
+        if not getattr(self.engine, "graph_enabled", False) or self.prediction_type != "epsilon":
             return None
         z_half = zt.dtype == torch.float16
         steps = []
@@ -503,7 +580,8 @@ class StableDiffusion:
 
     @torch.no_grad()
     def inversion(self, z0, uc, c, cfg_guidance: float = 1.0):
-        return self._ddim_loop(z0, uc, c, cfg_guidance, self.inversion_cfgpp, False, inversion=True, desc="DDIM Inversion")[1]
+        return self._ddim_loop(z0, uc, c, cfg_guidance, self.inversion_cfgpp, False, inversion=True, desc="DDIM Inversion",
+                               update=self._update_hook())[1]
 
     def _result(self, return_latents, latents, z):
         """what ``sample`` returns: ``latents`` when asked for them, else the decoded image of ``z``"""
@@ -561,6 +639,7 @@ class StableDiffusion:
             else:
                 self.engine.kdiff_input(x, xc, float(alphas[i].clone().sqrt()), 1)
             noise_uc, noise_c = self._predict(xc, new_t, uc, c, added)
+            self._eps_from_v(noise_uc, noise_c, xc, sigma)
             first = (solver == "euler") or (not have_old)
             coef, euler = K.kdiff_coeffs(cfg_guidance, sigmas, i, first, xl_form=xl_form, semantics=self.scalar_semantics)
             self.engine.step_kdiff(x, den, old, noise_uc, noise_c, coef, variant, xl_form, euler, solver != "euler")
@@ -592,6 +671,7 @@ class StableDiffusion:
             sigma_down, sigma_up = get_ancestral_step(sigmas[i], sigmas[i + 1])
             self.engine.kdiff_input(x, xc, K.kdiff_input_scale_sd(sigma, self.scalar_semantics), 0)
             noise_uc, noise_c = self.predict_noise(xc, new_t, uc, c)
+            self._eps_from_v(noise_uc, noise_c, xc, sigma)
             if (not two_stage) or float(sigma_down) == 0.0:
                 # Euler step down to sigma_down: x = den + ((x - d_from)/sigma) * sigma_down
                 # (`/ sigma.item()` in to_d, latent_diffusion.py:216-218, is a python-number divisor: K.divisor applies the backend rule)
@@ -610,6 +690,7 @@ class StableDiffusion:
                 t_2 = self.timestep(sigma_s)
                 self.engine.kdiff_input(x2, xc, K.kdiff_input_scale_sd(sigma_s, self.scalar_semantics), 0)
                 nuc2, nc2 = self.predict_noise(xc, t_2, uc, c)
+                self._eps_from_v(nuc2, nc2, xc, sigma_s)
                 self.engine.kdiff_denoise(x2, nuc2, nc2, lam, float(sigma_s), den2, uden2)
                 ratio_n = first(sigma_fn(t_next) / sigma_fn(t))
                 if cfgpp:   # x = den_2 - exp(-h) * uden_2 + ratio * x
@@ -632,6 +713,7 @@ def _sd_prompts(prompt):
 class BaseDDIM(StableDiffusion):
     """Basic DDIM solver for SD (reference: latent_diffusion.py:247-299)."""
     cfgpp = False
+    rescale_ok = True
 
     @torch.no_grad()
     @controlled
@@ -641,7 +723,8 @@ class BaseDDIM(StableDiffusion):
         zt = kwargs.get("latents")
         if zt is None:
             zt = self.initialize_latent(latent_dim=(B, self.cfg.out_channels) + self.latent_hw, seeds=kwargs.get("seeds"))
-        z0t, zt = self._ddim_loop(zt.to(self.work_device), uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn)
+        z0t, zt = self._ddim_loop(zt.to(self.work_device), uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn,
+                                  update=self._update_hook())
         return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
@@ -649,6 +732,7 @@ class BaseDDIM(StableDiffusion):
 class EulerCFGSolver(StableDiffusion):
     """Karras Euler, VE casted (reference: latent_diffusion.py:302-346)."""
     variant, solver = 0, "euler"
+    sigma_solver = True
 
     @torch.no_grad()
     @controlled
@@ -665,6 +749,7 @@ class EulerCFGSolver(StableDiffusion):
 class EulerAncestralCFGSolver(StableDiffusion):
     """Karras Euler + ancestral sampling (reference: latent_diffusion.py:349-390)."""
     cfgpp, two_stage = False, False
+    sigma_solver = True
 
     @torch.no_grad()
     @controlled
@@ -691,6 +776,7 @@ class DPMpp2mCFGSolver(EulerCFGSolver):
 class InversionDDIM(BaseDDIM):
     """Invert with CFG then reconstruct (reference: latent_diffusion.py:506-558)."""
     controllable = False
+    rescale_ok = False
 
     def _invert(self, src_img, uc, c, cfg_guidance, kwargs):
         z0 = kwargs.get("src_latent")
@@ -703,7 +789,7 @@ class InversionDDIM(BaseDDIM):
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, c = self._embeds(prompt, kwargs)
         zt = self._invert(src_img, uc, c, cfg_guidance, kwargs)
-        z0t, zt = self._ddim_loop(zt, uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn)
+        z0t, zt = self._ddim_loop(zt, uc, c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn, update=self._update_hook())
         return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 
@@ -717,7 +803,8 @@ class EditWordSwapDDIM(InversionDDIM):
     def sample(self, src_img=None, cfg_guidance=7.5, prompt=["", "", ""], callback_fn=None, **kwargs):
         uc, src_c, tgt_c = self._embeds(prompt, kwargs, n_cond=2)
         zt = self._invert(src_img, uc, src_c, cfg_guidance, kwargs)
-        z0t, zt = self._ddim_loop(zt, uc, tgt_c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn, desc="DDIM-edit")
+        z0t, zt = self._ddim_loop(zt, uc, tgt_c, cfg_guidance, False, self.cfgpp, callback_fn=callback_fn, desc="DDIM-edit",
+                                  update=self._update_hook())
         return self._result(kwargs.get("return_latents"), (z0t, zt), z0t)
 
 

@@ -210,7 +210,7 @@ class SDXL(StableDiffusion):
         """CFG / CFG++ inversion (reference: latent_sdxl.py:301-320 / 985-1004)."""
         self._split_cond_for_inversion(cfg_guidance, add_cond_kwargs)
         return self._ddim_loop(z0, uc, c, cfg_guidance, self.inversion_cfgpp, False, inversion=True, added=add_cond_kwargs,
-                               desc="DDIM inversion")[1]
+                               desc="DDIM inversion", update=self._update_hook())[1]
 
     def reverse_process(self, *args, **kwargs):
         raise NotImplementedError
@@ -241,6 +241,7 @@ class SDXLLightning(SDXL):
 class BaseDDIM(SDXL):
     """reference: latent_sdxl.py:425-467."""
     cfgpp = False
+    rescale_ok = True
 
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):
@@ -249,7 +250,7 @@ class BaseDDIM(SDXL):
             zt = self.initialize_latent(size=self._latent_size(shape), seeds=kwargs.get("seeds"))
         # unguarded alpha index (quirk Q3); for the last step, do not add noise: z0t
         return self._ddim_loop(zt, null_prompt_embeds, prompt_embeds, cfg_guidance, False, self.cfgpp, wrap=True,
-                               added=add_cond_kwargs, callback_fn=callback_fn, desc="SDXL")[0]
+                               added=add_cond_kwargs, callback_fn=callback_fn, desc="SDXL", update=self._update_hook())[0]
 
 
 @register_solver("euler")
@@ -257,6 +258,7 @@ class Euler(SDXL):
     """Karras Euler, VE casted (reference: latent_sdxl.py:469-517)."""
     quantize = True
     variant = 0
+    sigma_solver = True
 
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):
@@ -294,6 +296,7 @@ class EulerLight(_LightningMixin, Euler, SDXLLightning):
 class EditWardSwapDDIM(BaseDDIM):
     """Invert with the source prompt, regenerate with the target (reference: latent_sdxl.py:569-706)."""
     controllable = False
+    rescale_ok = False
 
     @torch.no_grad()
     @controlled
@@ -331,7 +334,7 @@ class EditWardSwapDDIM(BaseDDIM):
                                     add_cond_kwargs=add_src_cond_kwargs)
         # forward loop with the TARGET prompt; guarded alpha() here (latent_sdxl.py:679-703), unlike `ddim`
         return self._ddim_loop(zt, null_prompt_embeds, tgt_prompt_embed, cfg_guidance, False, self.cfgpp, wrap=False,
-                               added=add_tgt_cond_kwargs, callback_fn=callback_fn, desc="SDXL")[0]
+                               added=add_tgt_cond_kwargs, callback_fn=callback_fn, desc="SDXL", update=self._update_hook())[0]
 
 
 # ======== CFG++ solvers (renoise with eps_uc; small-lambda regime) ========
@@ -345,6 +348,7 @@ class BaseDDIMCFGpp(BaseDDIM):
 class EulerCFGpp(SDXL):
     """Euler CFG++ on the DDIM-timestep sigmas (reference: latent_sdxl.py:757-808)."""
     quantize = True
+    sigma_solver = True
 
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):
@@ -378,6 +382,7 @@ class DPMpp2mCFGppSolver(SDXL):
     c_in = sqrt(abar), c_out = -sigma, (uncond_denoised - old) in the 2nd-order term, returns x
     (reference: latent_sdxl.py:860-930)."""
     quantize = True
+    sigma_solver = True
 
     def reverse_process(self, null_prompt_embeds, prompt_embeds, cfg_guidance, add_cond_kwargs, shape=(1024, 1024),
                         callback_fn=None, **kwargs):

@@ -15,6 +15,7 @@ class Registry(dict):
             if name in self:
                 raise ValueError(f"{self.what} {name} already registered.")
             self[name] = cls
+            cls.solver_name = name          # what a refusal calls the solver
             return cls
         return add
 

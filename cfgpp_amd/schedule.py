@@ -75,6 +75,29 @@ def ddim_timesteps(num_sampling: int, steps_offset: int = 1) -> torch.Tensor:
     return torch.from_numpy(ts + steps_offset)
 
 
+def ddim_trailing_timesteps(num_sampling: int) -> torch.Tensor:
+    """DDIMScheduler.set_timesteps, "trailing" spacing: t_i = round(1000 - i*1000/N) - 1 -> int64 tensor."""
+    n = int(num_sampling)
+    ts = np.round(NUM_TRAIN_TIMESTEPS - np.arange(n) * NUM_TRAIN_TIMESTEPS / n) - 1
+    return torch.from_numpy(ts.astype(np.int64))
+
+
+def zero_terminal_snr_tables():
+    """(abar_z, sqrt(abar_z), sqrt(1-abar_z)), 1000 entries each, fp32: the table of diffusers' ``rescale_zero_terminal_snr``
+    (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", algorithm 1) in closed form,
+        abar_z[i] = ((sqrt(abar[i]) - sqrt(abar[999])) * sqrt(abar[0]) / (sqrt(abar[0]) - sqrt(abar[999])))^2,   abar_z[999] = 0,
+    from the pinned fp32 ``alphas_cumprod()`` in float64 with numpy, each table rounded ONCE to fp32.  IEEE basic operations and
+    sqrt in float64 are the same on every host, so these need no pinned data file."""
+    abar = alphas_cumprod().numpy().astype(np.float64)
+    r = np.sqrt(abar)
+    r0, rT = r[0], r[-1]
+    rz = (r - rT) * r0 / (r0 - rT)
+    rz[-1] = 0.0
+    az = rz * rz
+    f32 = lambda x: torch.from_numpy(x.astype(np.float32))  # noqa: E731
+    return f32(az), f32(np.sqrt(az)), f32(np.sqrt(1.0 - az))
+
+
 def euler_trailing_timesteps(num_sampling: int) -> torch.Tensor:
     """EulerDiscreteScheduler(timestep_spacing="trailing") -> fp32 tensor."""
     ts = np.round(np.arange(NUM_TRAIN_TIMESTEPS, 0, -NUM_TRAIN_TIMESTEPS / num_sampling)) - 1
@@ -109,17 +132,33 @@ class SchedulerTables:
     ``kind``: ``"ddim"`` (SD1.5 / SDXL base) or ``"lightning"`` (SDXL-Lightning).
     """
 
-    def __init__(self, num_sampling: int, kind: str = "ddim"):
+    def __init__(self, num_sampling: int, kind: str = "ddim", zero_terminal_snr: bool = False, timestep_spacing: str = "leading"):
+        """``zero_terminal_snr``: the rescaled table with abar[999] = 0 (:func:`zero_terminal_snr_tables`).
+        ``timestep_spacing``: "leading" (the reference's DDIM indexing, quirks Q1 / Q3 included: the default) or "trailing" -
+        diffusers' DDIMScheduler indexing, t_i = round(1000 - i*1000/N) - 1, alpha_t = abar[t], alpha_prev = abar[t - 1000//N] or
+        abar[0] when that index is negative (set_alpha_to_one = false), for both solver families (no shift, no wrap)."""
         if kind not in ("ddim", "lightning"):
             raise ValueError(f"unknown scheduler kind {kind}")
+        if timestep_spacing not in ("leading", "trailing"):
+            raise ValueError(f"timestep_spacing={timestep_spacing!r}: 'leading' or 'trailing'")
+        if zero_terminal_snr and timestep_spacing != "trailing":
+            raise ValueError("zero_terminal_snr=True needs timestep_spacing='trailing': under the shifted 'leading' table the zero entry "
+                             "abar[999] is never reached")
+        if kind == "lightning" and (zero_terminal_snr or timestep_spacing != "leading"):
+            raise ValueError("zero_terminal_snr / timestep_spacing='trailing' are not supported with the lightning scheduler")
         self.kind = kind
+        self.zero_terminal_snr = bool(zero_terminal_snr)
+        self.timestep_spacing = timestep_spacing
         self.num_sampling = int(num_sampling)
         self.total_alphas = alphas_cumprod()                       # abar, len 1000
+        if self.zero_terminal_snr:
+            self.total_alphas, sq_a, sq_1ma = zero_terminal_snr_tables()
         self.sigmas = (1 - self.total_alphas).sqrt() / self.total_alphas.sqrt()
         self.log_sigmas = self.sigmas.log()
         self.skip = NUM_TRAIN_TIMESTEPS // self.num_sampling
         if kind == "ddim":
-            self.timesteps = ddim_timesteps(self.num_sampling)     # int64
+            self.timesteps = ddim_timesteps(self.num_sampling) if timestep_spacing == "leading" \
+                else ddim_trailing_timesteps(self.num_sampling)     # int64
             self.final_alpha_cumprod = self.total_alphas[0].clone()
         else:
             self.timesteps = euler_trailing_timesteps(self.num_sampling)  # fp32
@@ -127,6 +166,9 @@ class SchedulerTables:
         # the shifted table (quirk Q1)
         self.alphas_cumprod = torch.cat([torch.tensor([1.0]), self.total_alphas])
         self._sqrt_a, self._sqrt_1ma = ddim_sqrt_tables()
+        if self.zero_terminal_snr:                                 # the same shifted layout over the rescaled table
+            self._sqrt_a = torch.cat([torch.tensor([1.0]), sq_a])
+            self._sqrt_1ma = torch.cat([torch.tensor([0.0]), sq_1ma])
 
     # -- reference index rules -------------------------------------------------
     def alpha(self, t) -> torch.Tensor:
@@ -157,8 +199,13 @@ class SchedulerTables:
         """(c1, c2, c3, c4) = sqrt(1-a_tw), sqrt(a_tw), sqrt(a_rn), sqrt(1-a_rn) as python floats
         (exact fp32 values) for the step at timestep ``t``:
         forward   a_tw = alpha(t),        a_rn = alpha(t - skip)   (latent_diffusion.py:655-666)
-        inversion a_tw = alpha(t - skip), a_rn = alpha(t)          (latent_diffusion.py:901-908)"""
-        i_t, i_p = self._index(t, wrap), self._index(int(t) - self.skip, wrap)
+        inversion a_tw = alpha(t - skip), a_rn = alpha(t)          (latent_diffusion.py:901-908)
+        Under "trailing" spacing alpha(t) = abar[t] and alpha(t - skip) = abar[t - skip], or abar[0] past the table's start;
+        ``wrap`` plays no part."""
+        if self.timestep_spacing == "trailing":
+            i_t, i_p = int(t) + 1, max(int(t) - self.skip, 0) + 1       # abar[k] is entry k + 1 of the shifted tables
+        else:
+            i_t, i_p = self._index(t, wrap), self._index(int(t) - self.skip, wrap)
         i_tw, i_rn = (i_p, i_t) if inversion else (i_t, i_p)
         return (float(self._sqrt_1ma[i_tw]), float(self._sqrt_a[i_tw]), float(self._sqrt_a[i_rn]), float(self._sqrt_1ma[i_rn]))
 

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass, field, replace
-from typing import Tuple
+from typing import Optional, Tuple
 
 
 @dataclass(frozen=True)
@@ -32,6 +32,7 @@ class UNetConfig:
     norm_groups: int = 32
     sample_size: int = 64          # default latent H = W
     vae_scale: float = 0.18215
+    linear_projection: Optional[bool] = None    # transformer proj_in / proj_out as linear layers; None: linear iff addition_embed
 
     @property
     def num_levels(self) -> int:
@@ -40,6 +41,12 @@ class UNetConfig:
     @property
     def temb_dim(self) -> int:
         return 4 * self.block_out_channels[0]
+
+    @property
+    def use_linear_projection(self) -> bool:
+        """diffusers' ``use_linear_projection``: SDXL and SD2.x checkpoints store proj_in / proj_out as [C, C] linear weights, SD1.5
+        as 1x1 convs"""
+        return bool(self.addition_embed) if self.linear_projection is None else bool(self.linear_projection)
 
 
 SD15 = UNetConfig(name="sd15")
@@ -61,7 +68,14 @@ SDXL_INPAINT = replace(SDXL, name="sdxl_inpaint", in_channels=9)
 TINY_SD_INPAINT = replace(TINY_SD, name="tiny_sd_inpaint", in_channels=9)
 TINY_XL_INPAINT = replace(TINY_XL, name="tiny_xl_inpaint", in_channels=9)
 
-CONFIGS = {c.name: c for c in (SD15, SDXL, TINY_SD, TINY_XL, SD15_INPAINT, SDXL_INPAINT, TINY_SD_INPAINT, TINY_XL_INPAINT)}
+# Stable Diffusion 2.x (stabilityai/stable-diffusion-2-1: 768-v, v-prediction; stable-diffusion-2-1-base: 512, epsilon; SD-Turbo): SD1.5's
+# topology with 64-wide heads (attention_head_dim = [5, 10, 20, 20]), the OpenCLIP-H context (1024) and linear projections
+SD21 = UNetConfig(name="sd21", num_heads=(5, 10, 20, 20), cross_attention_dim=1024, linear_projection=True, sample_size=96)
+SD21_BASE = replace(SD21, name="sd21_base", sample_size=64)
+TINY_SD2 = UNetConfig(name="tiny_sd2", block_out_channels=(64, 128, 128), level_has_attn=(1, 1, 0), transformer_depth=(1, 1, 1),
+                      num_heads=(1, 2, 2), cross_attention_dim=128, linear_projection=True, sample_size=12)
+
+CONFIGS = {c.name: c for c in (SD21, SD21_BASE, TINY_SD2, SD15, SDXL, TINY_SD, TINY_XL, SD15_INPAINT, SDXL_INPAINT, TINY_SD_INPAINT, TINY_XL_INPAINT)}
 INPAINT_OF = {"sd15": SD15_INPAINT, "sdxl": SDXL_INPAINT, "tiny_sd": TINY_SD_INPAINT, "tiny_xl": TINY_XL_INPAINT}
 
 
@@ -96,7 +110,7 @@ def param_shapes(cfg: UNetConfig) -> "OrderedDict[str, tuple]":
 
     def transformer(p, c, depth):
         norm(p + ".norm", c)
-        if cfg.addition_embed:           # SDXL: use_linear_projection=True
+        if cfg.use_linear_projection:    # SDXL, SD2.x: use_linear_projection=True
             lin(p + ".proj_in", c, c)
         else:                            # SD1.5: 1x1 convs
             conv(p + ".proj_in", c, c, 1)
@@ -115,7 +129,7 @@ def param_shapes(cfg: UNetConfig) -> "OrderedDict[str, tuple]":
             norm(b + ".norm3", c)
             lin(b + ".ff.net.0.proj", 8 * c, c)
             lin(b + ".ff.net.2", c, 4 * c)
-        if cfg.addition_embed:
+        if cfg.use_linear_projection:
             lin(p + ".proj_out", c, c)
         else:
             conv(p + ".proj_out", c, c, 1)

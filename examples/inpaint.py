@@ -50,6 +50,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--inpaint_unet", action="store_true", help="synthetic 9-channel inpaint UNet instead of the 4-channel one")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
+    from cfgpp_amd import vpred
+    vpred.add_cli_flags(ap)      # --prediction_type / --zero_terminal_snr / --timestep_spacing / --guidance_rescale
     args = ap.parse_args(argv)
     if args.mask_path is None:
         ap.error("--mask_path is required")
@@ -83,6 +85,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
     cli_kwargs(args, kw)
+    vpred.cli_kwargs(args, kw)        # explicit flags win over the checkpoint's files
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

@@ -51,6 +51,8 @@ def main(argv=None, solver_kwargs=None) -> None:
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
+    from cfgpp_amd import vpred
+    vpred.add_cli_flags(ap)      # --prediction_type / --zero_terminal_snr / --timestep_spacing / --guidance_rescale
     args = ap.parse_args(argv)
 
     from cfgpp_amd.callback_util import save_image
@@ -77,6 +79,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
     cli_kwargs(args, kw)
+    vpred.cli_kwargs(args, kw)        # explicit flags win over the checkpoint's files
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

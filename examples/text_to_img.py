@@ -64,6 +64,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
+    from cfgpp_amd import vpred
+    vpred.add_cli_flags(ap)      # --prediction_type / --zero_terminal_snr / --timestep_spacing / --guidance_rescale
     args = ap.parse_args(argv)
 
     from cfgpp_amd.callback_util import ComposeCallback, save_image
@@ -91,6 +93,7 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw.pop("lora_ignore_text_encoder", None)
     ip_kwargs = _ip_kwargs(args, kw)
     cli_kwargs(args, kw)
+    vpred.cli_kwargs(args, kw)        # explicit flags win over the checkpoint's files
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})

@@ -57,6 +57,8 @@ def main(argv=None, solver_kwargs=None) -> int:
     ap.add_argument("--no_draw", action="store_true", help="skip the per-step draw_noisy / draw_tweedie decodes")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
+    from cfgpp_amd import vpred
+    vpred.add_cli_flags(ap)      # --prediction_type / --zero_terminal_snr / --timestep_spacing / --guidance_rescale
     args = ap.parse_args(argv)
 
     from cfgpp_amd import dist
@@ -87,6 +89,7 @@ def main(argv=None, solver_kwargs=None) -> int:
         kw["lora"] = parse_cli(args.lora)          # replaces a LoRA file --model_dir found next to the model
         kw.pop("lora_ignore_text_encoder", None)
     cli_kwargs(args, kw)
+    vpred.cli_kwargs(args, kw)        # explicit flags win over the checkpoint's files
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     kw.update(solver_kwargs or {})
