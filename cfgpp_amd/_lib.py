@@ -87,6 +87,11 @@ IP_ADAPTER_PROTOTYPES = {
     "cfgpp_unet_image_context": (_I, [_P, _P, _I, _I, _F, _P]),
 }
 
+# the IP-Adapter "plus" extension header (include/cfgpp_ip_plus.h): the Resampler image projection
+IP_PLUS_PROTOTYPES = {
+    "cfgpp_unet_image_context_seq": (_I, [_P, _P, _I, _I, _I, _F, _P]),
+}
+
 # the long-prompt extension header (include/cfgpp_long_prompt.h)
 LONG_PROMPT_PROTOTYPES = {
     "cfgpp_unet_set_max_tokens": (_I, [_P, _I]),
@@ -124,6 +129,8 @@ DEBUG_PROTOTYPES = {
     "cfgpp_attention_set_cross_long": (None, [_I]),
     "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
+    "cfgpp_op_perceiver_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "cfgpp_unet_ip_tokens": (_I, [_P, _P, _I]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_add": (_I, [_P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -202,7 +209,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -28,6 +28,7 @@ SOURCES = [
     ("controlnet_kernels.hip", ["-ffp-contract=off"]),   # the residual add is torch's fp16 `s + r * scale` bit for bit
     ("lora_kernels.hip", []),
     ("freeu_kernel.hip", []),
+    ("resampler.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),     # as attn_kernel.hip: the scores are consumed by VALU
     ("unet.hip", []),
     ("vae.hip", []),
     ("text.hip", []),

@@ -100,6 +100,18 @@ int cfgpp_op_attention_clear_slots(void* k, void* vt, int BH, int d, int tok_pad
  * in between.  ip_scale == 0: the text-only call.  Refused, nothing launched: nk_text > 96, n_img > 32, k_tok_pad < 128. */
 int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int nk_text,
                           int n_img, float ip_scale, int q_tok_pad, int k_tok_pad, void* stream);
+/* Perceiver attention of the IP-Adapter "plus" Resampler (include/cfgpp_ip_plus.h; csrc/resampler.hip), head dim 64:
+ *   o[r][j][h*64 ..] = fp16( softmax_k(q[r][j][h] . k[r][k][h] / 8) v[r][k][h] ),  ONE softmax over the S keys of kv_x followed by the
+ *   n_q keys of kv_l.
+ * Token-major fp16 operands as the to_q / to_kv GEMMs store them, inner = heads * 64: q, o [rows][n_q][inner]; kv_x [rows][S][2 * inner]
+ * and kv_l [rows][n_q][2 * inner] with K in columns [0, inner) and V in [inner, 2 * inner).  One kernel instance, one wave per (row,
+ * head), 32-key tiles.  Refused by name, nothing launched: n_q outside 1 .. 32, S outside 1 .. 1024, a null operand. */
+int cfgpp_op_perceiver_attention(const void* q, const void* kv_x, const void* kv_l, void* o, int rows, int heads, int n_q, int S,
+                                 void* stream);
+/* the [rows][n_img][cross_attention_dim] fp16 image tokens the last cfgpp_unet_image_context / cfgpp_unet_image_context_seq computed
+ * (the output of the image projection, before the per-block to_k_ip / to_v_ip), copied to host_fp16_out.  rows must be the rows of
+ * that call.  Error when no tokens were computed since the adapter was loaded.  Synchronises the device. */
+int cfgpp_unet_ip_tokens(cfgpp_unet* u, void* host_fp16_out, int rows);
 int cfgpp_op_conv_in(const void* z, int z_is_half, void* out, const float* w, const float* bias,
                      int R, int zB, int Cin, int H, int W, int Cout, void* stream);
 /* conv_in of an inpaint UNet: input channels 0..Cz-1 from z (row r % zB), Cz..Cz+Cc-1 from the fp16 condition

@@ -56,6 +56,12 @@ int fanout_rows_launch(half_t* const* p, const long* row_elems, int nseg, int h,
 int lora_merge_launch(const half_t* base, half_t* dst, const float* up, const float* down, int rank, int kind, long O, long I,
                       int taps, hipStream_t s);
 
+// IP-Adapter "plus" Resampler (resampler.hip; used by unet.hip): perceiver attention over two token-major key / value sources, the
+// feed-forward's erf GELU in place, and the latents' broadcast to every batch row
+int perceiver_attn_launch(const half_t* q, const half_t* kvx, const half_t* kvl, half_t* o, int rows, int heads, int nq, int S, hipStream_t s);
+int gelu_inplace_launch(half_t* x, long n, hipStream_t s);
+int broadcast_rows_launch(const float* src, half_t* dst, long n, int rows, hipStream_t s);
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- activation layouts -----------------------------------------------------

@@ -10,6 +10,7 @@
 // launch plan (vector of closures) over preallocated, shape-keyed activation
 // buffers in halo-padded NHWC fp16 - no allocation, no host sync, one stream.
 #include "engine_base.h"
+#include "../../include/cfgpp_ip_plus.h"
 #include "freeu.h"
 
 struct cfgpp_unet : EngineBase {
@@ -134,12 +135,29 @@ struct cfgpp_unet : EngineBase {
     }
     // the profiler's tags of the cross-attention ops follow the token count of the current context
     void retag_cross() { if (plan_macs.size() == plan.size()) ip_set_active(ip_active, ip_n_img, ip_scale); }
+    // ---- the Resampler image projection of the "plus" adapters (include/cfgpp_ip_plus.h), an optional part of the adapter state.
+    // ip_kind: which image projection this adapter has - fixed by the first image_proj.* tensor after a drop.
+    enum { IP_NONE = 0, IP_LINEAR = 1, IP_RESAMPLER = 2 };
+    int ip_kind = IP_NONE;
+    enum { RG_LATENTS, RG_PIN_W, RG_PIN_B, RG_POUT_W, RG_POUT_B, RG_NOUT_W, RG_NOUT_B, RG_COUNT };
+    enum { RL_N1_W, RL_N1_B, RL_N2_W, RL_N2_B, RL_Q, RL_KV, RL_OUT, RL_FN_W, RL_FN_B, RL_FF1, RL_FF2, RL_COUNT };
+    static constexpr int RES_MAX_DEPTH = 8;
+    struct Resampler {
+        void* g[RG_COUNT] = {};                         // fp16 matrices [N][K]; fp32 biases, norms and latents
+        void* l[RES_MAX_DEPTH][RL_COUNT] = {};
+        int E = 0, D = 0, nq = 0, inner = 0, ff = 0;    // geometry as the tensors loaded so far fixed it (0: not yet)
+        // activations, fp16 (ip_malloc: adapter memory).  xs = {x, xn, kv_x}, sized by (max_rows, S_cap); the rest by max_rows
+        half_t* xs = nullptr; int S_cap = 0;
+        half_t* ls = nullptr;
+    } res;
+    int ip_seq = 0;                                     // Resampler: the seq of the hidden states the slots were computed from
     void ip_drop() {
         if (plan_macs.size() == plan.size()) ip_set_active(false, 0, 0.f);
         while (!ip_allocs.empty()) ip_free(ip_allocs.back().first);
         for (IpBlock& b : ip_blocks) { b.wkv = nullptr; b.has_k = b.has_v = false; }
         ip_wproj = nullptr; ip_bproj = nullptr; ip_ng = nullptr; ip_nb = nullptr; ip_proj_out = nullptr; ip_tok = nullptr;
         ip_proj_rows = ip_bias_rows = 0; ip_embed = 0; ip_tok_cap = 0; ip_src = nullptr; ip_rows = 0;
+        res = Resampler(); ip_kind = IP_NONE; ip_seq = 0;
     }
 };
 
@@ -877,6 +895,34 @@ int cfgpp_unet_image_condition(cfgpp_unet* u, const void* cond, int cond_rows, v
 // IPAdapterAttnProcessor2_0 per cross-attention with its own to_k_ip / to_v_ip.  No reference counterpart.
 static int ip_fail(const char* key, const char* why) { cfgpp_set_error("ip_load: %s: %s", key, why); return -2; }
 
+// The Resampler's tensors (include/cfgpp_ip_plus.h) by their published names under "image_proj." and what each axis is: a vector
+// has cdim -1; matrices are [rdim][cdim].  (latents [1, n_q, D]: the leading axes are taken off before the table is consulted.)
+enum { RK_D, RK_E, RK_INNER, RK_2INNER, RK_FF, RK_CROSS };
+struct ResSpec { const char* name; int rdim, cdim; };
+static const ResSpec RES_GLOBAL[cfgpp_unet::RG_COUNT] = {
+    {"latents", RK_D, -1}, {"proj_in.weight", RK_D, RK_E}, {"proj_in.bias", RK_D, -1}, {"proj_out.weight", RK_CROSS, RK_D},
+    {"proj_out.bias", RK_CROSS, -1}, {"norm_out.weight", RK_CROSS, -1}, {"norm_out.bias", RK_CROSS, -1}};
+static const ResSpec RES_LAYER[cfgpp_unet::RL_COUNT] = {
+    {"0.norm1.weight", RK_D, -1}, {"0.norm1.bias", RK_D, -1}, {"0.norm2.weight", RK_D, -1}, {"0.norm2.bias", RK_D, -1},
+    {"0.to_q.weight", RK_INNER, RK_D}, {"0.to_kv.weight", RK_2INNER, RK_D}, {"0.to_out.weight", RK_D, RK_INNER},
+    {"1.0.weight", RK_D, -1}, {"1.0.bias", RK_D, -1}, {"1.1.weight", RK_FF, RK_D}, {"1.3.weight", RK_D, RK_FF}};
+// "image_proj.<global>" -> (layer -1, slot); "image_proj.layers.<i>.<tail>" -> (i, slot), i unchecked
+static bool res_parse_key(const std::string& k, int& layer, int& slot) {
+    const std::string pre = "image_proj.";
+    if (k.compare(0, pre.size(), pre) != 0) return false;
+    const std::string rest = k.substr(pre.size());
+    for (int i = 0; i < cfgpp_unet::RG_COUNT; ++i)
+        if (rest == RES_GLOBAL[i].name) { layer = -1; slot = i; return true; }
+    if (rest.compare(0, 7, "layers.") != 0) return false;
+    size_t p = 7; long idx = 0;
+    while (p < rest.size() && rest[p] >= '0' && rest[p] <= '9' && p < 7 + 6) idx = idx * 10 + (rest[p++] - '0');
+    if (p == 7 || p >= rest.size() || rest[p] != '.') return false;
+    const std::string tail = rest.substr(p + 1);
+    for (int i = 0; i < cfgpp_unet::RL_COUNT; ++i)
+        if (tail == RES_LAYER[i].name) { layer = (int)idx; slot = i; return true; }
+    return false;
+}
+
 int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dtype, const long* shape, int ndim) {
     CFGPP_REQUIRE(u && u->finalized, "ip_load: the engine is not finalized (the adapter attaches to the uploaded UNet)");
     CFGPP_REQUIRE(!u->control, "ip_load: a ControlNet takes no image tokens (diffusers passes it the text context only)");
@@ -914,6 +960,75 @@ int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dty
         return 0;
     };
     auto changed = [&]() { if (u->ip_active) u->ip_set_active(false, 0, 0.f); u->ip_src = nullptr; };      // the slots are stale now
+    // an adapter has ONE image projection: the first image_proj.* tensor after a drop fixes the kind
+    const bool linear_key = k == "image_proj.proj.weight" || k == "image_proj.proj.bias" || k == "image_proj.norm.weight" || k == "image_proj.norm.bias";
+    int res_layer = -1, res_slot = -1;
+    const bool res_key = res_parse_key(k, res_layer, res_slot);
+    if ((linear_key && u->ip_kind == cfgpp_unet::IP_RESAMPLER) || (res_key && u->ip_kind == cfgpp_unet::IP_LINEAR)) {
+        cfgpp_set_error("ip_load: %s: a tensor of the %s image projection, but this adapter's first image_proj tensor made it a %s adapter: drop it "
+                        "(key == NULL) first", key, linear_key ? "Linear + LayerNorm" : "Resampler (\"plus\")", linear_key ? "Resampler (\"plus\")" : "Linear + LayerNorm");
+        return -2;
+    }
+    if (res_key && res_layer >= cfgpp_unet::RES_MAX_DEPTH) {
+        cfgpp_set_error("ip_load: %s: layer %d, the Resampler may have 1 .. %d layers", key, res_layer, cfgpp_unet::RES_MAX_DEPTH);
+        return -2;
+    }
+    if (res_key) {
+        // Resampler tensor: its shape must fit the UNet and the geometry the tensors loaded so far fixed (every layer has layer 0's shapes)
+        const ResSpec& sp = res_layer < 0 ? RES_GLOBAL[res_slot] : RES_LAYER[res_slot];
+        cfgpp_unet::Resampler g = u->res;           // the geometry with this tensor, committed after the upload
+        long dim[2] = {0, 0}; int nd = ndim;
+        const long* sh = shape;
+        if (res_layer < 0 && res_slot == cfgpp_unet::RG_LATENTS) {
+            if (ndim == 3 && shape[0] == 1) { sh = shape + 1; nd = 2; }
+            if (nd != 2 || sh[0] < 1 || sh[0] > cfgpp_unet::IP_MAX) {
+                cfgpp_set_error("ip_load: %s: shape [%ld, %ld, %ld], expected [1, n_q, D] with 1 <= n_q <= %d image tokens", key, ndim > 0 ? shape[0] : 0,
+                                ndim > 1 ? shape[1] : 0, ndim > 2 ? shape[2] : 0, cfgpp_unet::IP_MAX);
+                return -2;
+            }
+            if (g.nq && g.nq != sh[0]) { cfgpp_set_error("ip_load: %s: n_q %ld, the latents loaded before have %d", key, sh[0], g.nq); return -2; }
+            g.nq = (int)sh[0]; sh += 1; nd = 1;      // the remaining axis is D
+        }
+        if (nd != (sp.cdim >= 0 ? 2 : 1)) { cfgpp_set_error("ip_load: %s: %d axes, expected %d", key, ndim, sp.cdim >= 0 ? 2 : 1); return -2; }
+        dim[0] = sh[0]; dim[1] = nd > 1 ? sh[1] : 0;
+        const int kinds[2] = {sp.rdim, sp.cdim};
+        for (int ax = 0; ax < nd; ++ax) {
+            static const char* const NAMES[] = {"D", "E", "inner", "inner", "ff_inner", "cross_attention_dim"};
+            long got = dim[ax]; const int kd = kinds[ax];
+            if (kd == RK_CROSS) {
+                if (got != cross) { cfgpp_set_error("ip_load: %s: shape [%ld, %ld], axis %d must be the UNet's cross_attention_dim = %ld", key, dim[0], dim[1], ax, cross); return -2; }
+                continue;
+            }
+            if (kd == RK_2INNER) {
+                if (got % 2 != 0 || (g.inner && got != 2L * g.inner)) {
+                    cfgpp_set_error("ip_load: %s: %ld rows, to_kv has 2 * inner = %d rows (K rows, then V rows)", key, got, 2 * g.inner); return -2;
+                }
+                got /= 2;
+            }
+            int& known = kd == RK_D ? g.D : kd == RK_E ? g.E : kd == RK_FF ? g.ff : g.inner;
+            if (got < 64 || got % 64 != 0) {
+                cfgpp_set_error("ip_load: %s: shape [%ld, %ld]: %s = %ld must be a positive multiple of 64", key, dim[0], dim[1], NAMES[kd], got); return -2;
+            }
+            if (known && known != got) {
+                cfgpp_set_error("ip_load: %s: shape [%ld, %ld]: %s = %ld, the tensors loaded before have %s = %d (every layer has layer 0's shapes)", key, dim[0],
+                                dim[1], NAMES[kd], got, NAMES[kd], known);
+                return -2;
+            }
+            known = (int)got;
+        }
+        void** slot = res_layer < 0 ? &u->res.g[res_slot] : &u->res.l[res_layer][res_slot];
+        if (sp.cdim >= 0) {
+            std::vector<half_t> h; to_half(h);
+            if (int e = put(slot, h.data(), h.size() * sizeof(half_t))) return e;
+        } else {
+            std::vector<float> f; to_float(f);
+            if (int e = put(slot, f.data(), f.size() * sizeof(float))) return e;
+        }
+        u->res.E = g.E; u->res.D = g.D; u->res.nq = g.nq; u->res.inner = g.inner; u->res.ff = g.ff;
+        u->ip_kind = cfgpp_unet::IP_RESAMPLER;
+        changed();
+        return 0;
+    }
     if (k == "image_proj.proj.weight") {
         if (ndim != 2 || shape[0] % cross != 0 || shape[0] / cross < 1 || shape[0] / cross > cfgpp_unet::IP_MAX || shape[1] < 64 || shape[1] % 64 != 0) {
             cfgpp_set_error("ip_load: %s: shape [%ld, %ld], expected [n_img * %ld, embed_dim] with 1 <= n_img <= %d image tokens and embed_dim a "
@@ -923,7 +1038,7 @@ int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dty
         std::vector<half_t> h; to_half(h);
         if (int e = put((void**)&u->ip_wproj, h.data(), h.size() * sizeof(half_t))) return e;
         u->ip_proj_rows = shape[0]; u->ip_embed = (int)shape[1];
-        changed();
+        u->ip_kind = cfgpp_unet::IP_LINEAR; changed();
         return 0;
     }
     if (k == "image_proj.proj.bias") {
@@ -933,14 +1048,14 @@ int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dty
         std::vector<float> f; to_float(f);
         if (int e = put((void**)&u->ip_bproj, f.data(), f.size() * sizeof(float))) return e;
         u->ip_bias_rows = shape[0];
-        changed();
+        u->ip_kind = cfgpp_unet::IP_LINEAR; changed();
         return 0;
     }
     if (k == "image_proj.norm.weight" || k == "image_proj.norm.bias") {
         if (ndim != 1 || shape[0] != cross) { cfgpp_set_error("ip_load: %s: %ld elements, expected cross_attention_dim = %ld", key, n, cross); return -2; }
         std::vector<float> f; to_float(f);
         if (int e = put((void**)(k == "image_proj.norm.weight" ? &u->ip_ng : &u->ip_nb), f.data(), f.size() * sizeof(float))) return e;
-        changed();
+        u->ip_kind = cfgpp_unet::IP_LINEAR; changed();
         return 0;
     }
     for (int part = 0; part < 2; ++part) {
@@ -967,8 +1082,24 @@ int cfgpp_unet_ip_load(cfgpp_unet* u, const char* key, const void* host, int dty
         }
     }
     cfgpp_set_error("ip_load: unknown key %s (image_proj.proj.{weight,bias}, image_proj.norm.{weight,bias}, <transformer block>.attn2.to_k_ip.weight / "
-                    ".to_v_ip.weight)", key);
+                    ".to_v_ip.weight; Resampler adapters: the image_proj.* keys of include/cfgpp_ip_plus.h)", key);
     return -3;
+}
+
+// the per-block half of an image context: u->ip_tok [rows][n_img][cross] -> every cross-attention's image K / V^T slots
+static int ip_project_blocks(cfgpp_unet* u, int rows, int n_img, hipStream_t s) {
+    const int cross = u->cfg.cross_attention_dim;
+    for (const auto& b : u->ip_blocks) {
+        // slots [96, 128) cleared first: a smaller n_img after a larger one leaves no stale keys
+        if (int e = cfgpp_op_attention_clear_slots(b.ck, b.cvt, u->max_rows * b.nheads, b.d, u->ip_ck_pad, cfgpp_unet::IP_SLOT, cfgpp_unet::IP_MAX, s)) return e;
+        IGemmArgs a = base_args(u);     // the form of the text K / V^T launch of ctx_plan, the image tokens as the batch's rows
+        a.a0 = u->ip_tok; a.C0 = cross; a.amode = 0; a.w = b.wkv; a.N = 2 * b.C; a.K = cross; a.epi = EPI_HEADS;
+        a.hq = nullptr; a.hk = b.ck + (size_t)cfgpp_unet::IP_SLOT * b.dp; a.hvt = b.cvt + cfgpp_unet::IP_SLOT;
+        a.part0 = 1; a.part_width = b.C; a.head_dim = b.d; a.head_dim_pad = b.dp; a.heads = b.nheads;
+        a.tok_pad = u->ip_ck_pad; a.q_tok_pad = u->ip_ck_pad; a.rows_per_batch = n_img; a.M = rows * n_img;
+        if (int e = igemm_launch(a, s)) return e;
+    }
+    return 0;
 }
 
 // Replaces, per job instead of per step and per block: `image_embeds = self.encoder_hid_proj(image_embeds)` (ImageProjection.forward)
@@ -982,6 +1113,8 @@ int cfgpp_unet_image_context(cfgpp_unet* u, const void* image_embeds, int rows, 
         if (u->ip_active) u->ip_set_active(false, 0, 0.f);
         return 0;
     }
+    CFGPP_REQUIRE(u->ip_kind != cfgpp_unet::IP_RESAMPLER, "image_context: the loaded adapter is a Resampler (\"plus\") adapter: call "
+                  "cfgpp_unet_image_context_seq with the image tower's hidden states [rows][seq][embed_dim] (include/cfgpp_ip_plus.h)");
     {
         std::string miss; int nm = 0;
         auto need = [&](bool have, const std::string& name) { if (!have) { if (nm < 8) miss += name + " "; ++nm; } };
@@ -1018,19 +1151,118 @@ int cfgpp_unet_image_context(cfgpp_unet* u, const void* image_embeds, int rows, 
             if (int e = igemm_launch(a, s)) return e;
             if (int e = cfgpp_op_layernorm(u->ip_proj_out, u->ip_tok, u->ip_ng, u->ip_nb, (long)rows * n_img, cross, 1e-5f, s)) return e;
         }
-        for (const auto& b : u->ip_blocks) {
-            // slots [96, 128) cleared first: a smaller n_img after a larger one leaves no stale keys
-            if (int e = cfgpp_op_attention_clear_slots(b.ck, b.cvt, u->max_rows * b.nheads, b.d, u->ip_ck_pad, cfgpp_unet::IP_SLOT, cfgpp_unet::IP_MAX, s)) return e;
-            IGemmArgs a = base_args(u);     // the form of the text K / V^T launch of ctx_plan, the image tokens as the batch's rows
-            a.a0 = u->ip_tok; a.C0 = cross; a.amode = 0; a.w = b.wkv; a.N = 2 * b.C; a.K = cross; a.epi = EPI_HEADS;
-            a.hq = nullptr; a.hk = b.ck + (size_t)cfgpp_unet::IP_SLOT * b.dp; a.hvt = b.cvt + cfgpp_unet::IP_SLOT;
-            a.part0 = 1; a.part_width = b.C; a.head_dim = b.d; a.head_dim_pad = b.dp; a.heads = b.nheads;
-            a.tok_pad = u->ip_ck_pad; a.q_tok_pad = u->ip_ck_pad; a.rows_per_batch = n_img; a.M = rows * n_img;
-            if (int e = igemm_launch(a, s)) return e;
-        }
+        if (int e = ip_project_blocks(u, rows, n_img, s)) return e;
         u->ip_src = image_embeds; u->ip_rows = rows;
     }
     u->ip_set_active(true, n_img, scale);
+    return 0;
+}
+
+// The Resampler form of the call above (include/cfgpp_ip_plus.h): replaces, per job, `image_embeds = self.encoder_hid_proj(image_embeds)`
+// with encoder_hid_proj an IP-Adapter Resampler (PerceiverAttention + FeedForward layers over learned latents).  Dataflow, all fp16
+// between launches (x, xn, kv_x sized by seq; the rest by n_q):
+//   x = proj_in(hidden) + b                                      GEMM, bias in the epilogue
+//   lat = fp16(latents) for every row                            broadcast_rows
+//   per layer:  xn = LN(x; norm1)   ln = LN(lat; norm2)          cfgpp_op_layernorm
+//               q = to_q(ln)   kv_x = to_kv(xn)   kv_l = to_kv(ln)      three GEMMs, token-major outputs
+//               att = perceiver attention(q, kv_x, kv_l)          resampler.hip, reads those outputs as they are
+//               lat = to_out(att) + lat                           GEMM, residual in the epilogue (in place)
+//               ln = LN(lat; ff norm)   ff = W1(ln)   ff = gelu_erf(ff)   lat = W2(ff) + lat
+//   tokens = LN(proj_out(lat) + b; norm_out)  -> u->ip_tok
+int cfgpp_unet_image_context_seq(cfgpp_unet* u, const void* hidden, int rows, int seq, int embed_dim, float scale, void* stream) {
+    CFGPP_REQUIRE(u && u->finalized, "image_context_seq: engine not finalized");
+    CFGPP_REQUIRE(!u->control, "image_context_seq: a ControlNet takes no image tokens");
+    if (!hidden || scale == 0.f) {                  // deactivate: the next forward is the text-only plan, launch for launch
+        if (u->ip_active) u->ip_set_active(false, 0, 0.f);
+        return 0;
+    }
+    CFGPP_REQUIRE(u->ip_kind != cfgpp_unet::IP_LINEAR, "image_context_seq: the loaded adapter has a Linear + LayerNorm image projection: call "
+                  "cfgpp_unet_image_context with the pooled embeds [rows][embed_dim]");
+    cfgpp_unet::Resampler& R = u->res;
+    int depth = 0;
+    for (int i = 0; i < cfgpp_unet::RES_MAX_DEPTH; ++i)
+        for (int j = 0; j < cfgpp_unet::RL_COUNT; ++j) if (R.l[i][j]) depth = i + 1;
+    {
+        std::string miss; int nm = 0;
+        auto need = [&](bool have, const std::string& name) { if (!have) { if (nm < 8) miss += name + " "; ++nm; } };
+        for (int j = 0; j < cfgpp_unet::RG_COUNT; ++j) need(R.g[j], std::string("image_proj.") + RES_GLOBAL[j].name);
+        for (int i = 0; i < (depth ? depth : 1); ++i)
+            for (int j = 0; j < cfgpp_unet::RL_COUNT; ++j) need(R.l[i][j], "image_proj.layers." + std::to_string(i) + "." + RES_LAYER[j].name);
+        for (const auto& b : u->ip_blocks) { need(b.has_k, b.name + ".to_k_ip.weight"); need(b.has_v, b.name + ".to_v_ip.weight"); }
+        if (nm) { cfgpp_set_error("image_context_seq: missing %d adapter tensors (cfgpp_unet_ip_load): %s%s", nm, miss.c_str(), nm > 8 ? "..." : ""); return -2; }
+    }
+    CFGPP_REQUIRE(embed_dim == R.E, "image_context_seq: embed_dim=%d, the adapter's image_proj.proj_in takes %d", embed_dim, R.E);
+    CFGPP_REQUIRE(seq >= 1 && seq <= 1024, "image_context_seq: seq=%d (1 .. 1024 hidden-state tokens per row)", seq);
+    CFGPP_REQUIRE(u->ctx_set && rows == u->ctx_rows, "image_context_seq: rows=%d must equal the rows of the current text context (%d): call "
+                  "cfgpp_unet_set_context first", rows, u->ctx_set ? u->ctx_rows : 0);
+    const int cross = u->cfg.cross_attention_dim, nq = R.nq, D = R.D, inner = R.inner, ff = R.ff, heads = R.inner / 64;
+    hipStream_t s = (hipStream_t)stream;
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    if (!(u->ip_src == hidden && u->ip_rows == rows && u->ip_seq == seq)) {     // (a new scale alone keeps the projected K / V^T)
+        const long Ml_cap = (long)u->max_rows * nq;
+        if (!R.ls || !u->ip_tok) {
+            CFGPP_HIP_CHECK(hipDeviceSynchronize());
+            if (!R.ls) R.ls = (half_t*)u->ip_malloc((size_t)Ml_cap * (2 * D + 4 * inner + ff + cross) * sizeof(half_t));
+            if (!u->ip_tok) u->ip_tok = (half_t*)u->ip_malloc((size_t)Ml_cap * cross * sizeof(half_t));
+            u->ip_tok_cap = (R.ls && u->ip_tok) ? Ml_cap * cross : 0;
+            CFGPP_REQUIRE(u->ip_tok_cap, "image_context_seq: out of device memory");
+        }
+        if (R.S_cap < seq) {                        // the seq-sized activations grow, never shrink
+            CFGPP_HIP_CHECK(hipDeviceSynchronize());
+            if (R.xs) u->ip_free(R.xs);
+            R.xs = (half_t*)u->ip_malloc((size_t)u->max_rows * seq * (2 * D + 2 * inner) * sizeof(half_t));
+            R.S_cap = R.xs ? seq : 0;
+            CFGPP_REQUIRE(R.xs, "image_context_seq: out of device memory");
+        }
+        u->ip_src = nullptr;
+        const int Mx = rows * seq, Ml = rows * nq;
+        half_t* x = R.xs; half_t* xn = x + (long)Mx * D; half_t* kvx = xn + (long)Mx * D;
+        half_t* lat = R.ls; half_t* ln = lat + (long)Ml * D; half_t* q = ln + (long)Ml * D; half_t* kvl = q + (long)Ml * inner;
+        half_t* att = kvl + (long)Ml * 2 * inner; half_t* ffb = att + (long)Ml * inner; half_t* po = ffb + (long)Ml * ff;
+        auto gemm = [&](const half_t* A, int tokens, int K, const void* w, int N, const void* bias, const half_t* resid, half_t* out) {
+            IGemmArgs a = base_args(u);
+            a.a0 = A; a.C0 = K; a.amode = 0; a.w = (const half_t*)w; a.N = N; a.K = K; a.bias = (const float*)bias;
+            a.resid = resid; a.rmode = 0; a.rld = N; a.out = out; a.omode = 0; a.old = N; a.epi = EPI_STORE;
+            a.rows_per_batch = tokens; a.M = rows * tokens;
+            return igemm_launch(a, s);
+        };
+        auto norm = [&](const half_t* in, half_t* out, const void* g, const void* b, long n, int C) {
+            return cfgpp_op_layernorm(in, out, (const float*)g, (const float*)b, n, C, 1e-5f, s);
+        };
+        if (int e = gemm((const half_t*)hidden, seq, embed_dim, R.g[cfgpp_unet::RG_PIN_W], D, R.g[cfgpp_unet::RG_PIN_B], nullptr, x)) return e;
+        if (int e = broadcast_rows_launch((const float*)R.g[cfgpp_unet::RG_LATENTS], lat, (long)nq * D, rows, s)) return e;
+        for (int i = 0; i < depth; ++i) {
+            void* const* L = R.l[i];
+            if (int e = norm(x, xn, L[cfgpp_unet::RL_N1_W], L[cfgpp_unet::RL_N1_B], Mx, D)) return e;
+            if (int e = norm(lat, ln, L[cfgpp_unet::RL_N2_W], L[cfgpp_unet::RL_N2_B], Ml, D)) return e;
+            if (int e = gemm(ln, nq, D, L[cfgpp_unet::RL_Q], inner, nullptr, nullptr, q)) return e;
+            if (int e = gemm(xn, seq, D, L[cfgpp_unet::RL_KV], 2 * inner, nullptr, nullptr, kvx)) return e;
+            if (int e = gemm(ln, nq, D, L[cfgpp_unet::RL_KV], 2 * inner, nullptr, nullptr, kvl)) return e;
+            if (int e = perceiver_attn_launch(q, kvx, kvl, att, rows, heads, nq, seq, s)) return e;
+            if (int e = gemm(att, nq, inner, L[cfgpp_unet::RL_OUT], D, nullptr, lat, lat)) return e;
+            if (int e = norm(lat, ln, L[cfgpp_unet::RL_FN_W], L[cfgpp_unet::RL_FN_B], Ml, D)) return e;
+            if (int e = gemm(ln, nq, D, L[cfgpp_unet::RL_FF1], ff, nullptr, nullptr, ffb)) return e;
+            if (int e = gelu_inplace_launch(ffb, (long)Ml * ff, s)) return e;
+            if (int e = gemm(ffb, nq, ff, L[cfgpp_unet::RL_FF2], D, nullptr, lat, lat)) return e;
+        }
+        if (int e = gemm(lat, nq, D, R.g[cfgpp_unet::RG_POUT_W], cross, R.g[cfgpp_unet::RG_POUT_B], nullptr, po)) return e;
+        if (int e = norm(po, u->ip_tok, R.g[cfgpp_unet::RG_NOUT_W], R.g[cfgpp_unet::RG_NOUT_B], Ml, cross)) return e;
+        if (int e = ip_project_blocks(u, rows, nq, s)) return e;
+        u->ip_src = hidden; u->ip_rows = rows; u->ip_seq = seq;
+    }
+    u->ip_set_active(true, nq, scale);
+    return 0;
+}
+
+int cfgpp_unet_ip_tokens(cfgpp_unet* u, void* host_fp16_out, int rows) {
+    CFGPP_REQUIRE(u && u->finalized && host_fp16_out, "ip_tokens: null engine / output");
+    CFGPP_REQUIRE(u->ip_tok && u->ip_src, "ip_tokens: no image tokens computed since the adapter was loaded (cfgpp_unet_image_context / _seq)");
+    CFGPP_REQUIRE(rows == u->ip_rows, "ip_tokens: rows=%d, the last image context had %d", rows, u->ip_rows);
+    const long cross = u->cfg.cross_attention_dim;
+    const long n_img = u->ip_kind == cfgpp_unet::IP_RESAMPLER ? u->res.nq : u->ip_proj_rows / cross;
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    CFGPP_HIP_CHECK(hipDeviceSynchronize());
+    CFGPP_HIP_CHECK(hipMemcpy(host_fp16_out, u->ip_tok, (size_t)rows * n_img * cross * sizeof(half_t), hipMemcpyDeviceToHost));
     return 0;
 }
 

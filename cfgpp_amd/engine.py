@@ -411,24 +411,37 @@ class HipUNet:
 
     def set_image_context(self, image_embeds: Optional[torch.Tensor], scale: float = 1.0):
         """image_embeds [rows, embed_dim] (uc rows first, then c rows; rows of the current text context); None or scale 0
-        deactivates (include/cfgpp_ip_adapter.h: cfgpp_unet_image_context).  The engine identifies the embeds by address, so the tensor
-        of the last call is kept alive here and an equal tensor is not copied again."""
+        deactivates (include/cfgpp_ip_adapter.h: cfgpp_unet_image_context).  A 3-D tensor [rows, seq, embed_dim] is the image tower's
+        hidden states for a Resampler ("plus") adapter (include/cfgpp_ip_plus.h: cfgpp_unet_image_context_seq); the engine refuses
+        the form that does not fit the loaded adapter's kind.  The engine identifies the embeds by address, so the tensor of the
+        last call is kept alive here and an equal tensor is not copied again."""
         dev = torch.device("cuda", self.device)
         stream = torch.cuda.current_stream(dev).cuda_stream
         if image_embeds is None or float(scale) == 0.0:
             check(self.lib.cfgpp_unet_image_context(self._h, None, 0, 0, 0.0, stream), "cfgpp_unet_image_context")
             return
         e = image_embeds.to(device=dev, dtype=torch.float16).contiguous()
-        if e.dim() != 2:
-            raise CfgppError(f"set_image_context: image_embeds shape {tuple(e.shape)}, expected [rows, embed_dim]")
+        if e.dim() not in (2, 3):
+            raise CfgppError(f"set_image_context: image_embeds shape {tuple(e.shape)}, expected [rows, embed_dim] (Linear adapters) or "
+                             "[rows, seq, embed_dim] (Resampler adapters)")
         old = self._keep.get("ip_embeds")
         if old is not None and old.shape == e.shape and bool(torch.equal(old, e)):
             e = old                         # the same values: only the scale changes, nothing is projected again
         else:
             e = e.clone()                   # a private copy (the old one is still alive: a new address), safe from in-place edits
-        check(self.lib.cfgpp_unet_image_context(self._h, e.data_ptr(), int(e.shape[0]), int(e.shape[1]), float(scale), stream),
-              "cfgpp_unet_image_context")
+        if e.dim() == 3:                    # hidden states for a Resampler adapter (include/cfgpp_ip_plus.h)
+            check(self.lib.cfgpp_unet_image_context_seq(self._h, e.data_ptr(), int(e.shape[0]), int(e.shape[1]), int(e.shape[2]), float(scale),
+                                                        stream), "cfgpp_unet_image_context_seq")
+        else:
+            check(self.lib.cfgpp_unet_image_context(self._h, e.data_ptr(), int(e.shape[0]), int(e.shape[1]), float(scale), stream),
+                  "cfgpp_unet_image_context")
         self._keep["ip_embeds"] = e
+
+    def ip_tokens(self, rows: int, n_img: int) -> torch.Tensor:
+        """the [rows, n_img, cross_attention_dim] fp16 image tokens of the last image context (csrc/cfgpp_debug.h: cfgpp_unet_ip_tokens)"""
+        out = torch.empty((int(rows), int(n_img), self.cfg.cross_attention_dim), dtype=torch.float16)
+        check(self.lib.cfgpp_unet_ip_tokens(self._h, out.data_ptr(), int(rows)), "cfgpp_unet_ip_tokens")
+        return out
 
     def set_freeu(self, spec):
         """diffusers' ``enable_freeu(s1, s2, b1, b2)`` (``spec`` = that tuple, or a mapping with those keys) / ``disable_freeu()``

@@ -157,17 +157,21 @@ class HipEngine:
         return self._ip
 
     def set_image_embeds(self, embeds: Optional[torch.Tensor], negative: Optional[torch.Tensor] = None, scale: float = 1.0):
-        """image prompt of the next predictions: ``embeds`` [1 or B, embed_dim] (None deactivates), ``negative`` None = zeros; call
-        after ``set_context`` (the rows are the text context's)."""
+        """image prompt of the next predictions: ``embeds`` [1 or B, embed_dim] - for a Resampler ("plus") adapter the image tower's
+        penultimate hidden states [1 or B, seq, embed_dim] - (None deactivates), ``negative`` None = zeros of the same shape; call after
+        ``set_context`` (the rows are the text context's)."""
         if embeds is None or float(scale) == 0.0:
             self.unet.set_image_context(None)
             return
         if self.ip_adapter is None:
             raise CfgppError("ip_adapter_image_embeds given but no IP-Adapter is loaded (get_solver(..., ip_adapter=...) / set_ip_adapter)")
-        from .ip_adapter import assemble_embeds
+        from .ip_adapter import assemble_embeds, assemble_hidden
         if int(embeds.shape[-1]) != self.ip_adapter.embed_dim:
             raise CfgppError(f"ip_adapter_image_embeds: embed_dim {int(embeds.shape[-1])}, the adapter takes {self.ip_adapter.embed_dim}")
-        self.unet.set_image_context(assemble_embeds(embeds, negative, self.B), float(scale))
+        if self.ip_adapter.seq_input:
+            self.unet.set_image_context(assemble_hidden(embeds, negative, self.B), float(scale))
+        else:
+            self.unet.set_image_context(assemble_embeds(embeds, negative, self.B), float(scale))
 
     # -- FreeU -----------------------------------------------------------------------
     def set_freeu(self, spec):

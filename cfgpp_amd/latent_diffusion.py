@@ -318,7 +318,14 @@ class StableDiffusion:
                     raise ValueError("ip_adapter_image needs the CLIP image encoder: get_solver(..., ip_adapter_dir=<folder holding image_encoder/>)")
                 from .ip_adapter import ImageEncoder
                 self.image_encoder = ImageEncoder(self.ip_adapter_dir, self.work_device)
-            emb = self.image_encoder(img)
+            if getattr(self.engine.ip_adapter, "seq_input", False):
+                # a Resampler ("plus") adapter reads the tower's penultimate hidden states; its default negative is the tower on an
+                # all-zero pixel tensor (the published pipeline's zeros_like of the preprocessed image), not zero hidden states
+                emb = self.image_encoder(img, hidden=True)
+                if neg is None:
+                    neg = self.image_encoder.negative_hidden(img)
+            else:
+                emb = self.image_encoder(img)
         self._ip_serial += 1
         return (emb, neg, float(scale), self._ip_serial)
 

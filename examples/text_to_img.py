@@ -105,12 +105,12 @@ def main(argv=None, solver_kwargs=None) -> None:
         solver = get_solver(args.method, **kw)
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
                                cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver), **ip_kwargs)
+                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
         solver = get_solver(args.method, **kw)
         result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver), **ip_kwargs)
+                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
 
     for i in range(result.shape[0]):
         name = "generated.png" if result.shape[0] == 1 else f"generated_{i}.png"
@@ -135,7 +135,7 @@ def _ip_kwargs(args, kw):
     if args.ip_embeds:
         import numpy as np
         emb = torch.from_numpy(np.load(args.ip_embeds)).float()
-        return dict(ip_adapter_image_embeds=emb.reshape(-1, emb.shape[-1]), ip_adapter_scale=scale)
+        return dict(ip_adapter_image_embeds=emb, ip_adapter_scale=scale)       # shaped by _ip_fit_embeds once the adapter's kind is known
     if not args.ip_adapter_dir:
         raise SystemExit("--ip_image needs --ip_adapter_dir (the folder that holds the CLIP image_encoder/)")
     kw["ip_adapter_dir"] = args.ip_adapter_dir
@@ -143,6 +143,22 @@ def _ip_kwargs(args, kw):
     import numpy as np
     img = torch.from_numpy(np.asarray(Image.open(args.ip_image).convert("RGB"), dtype=np.float32) / 255.0).permute(2, 0, 1)[None].contiguous()
     return dict(ip_adapter_image=img, ip_adapter_scale=scale)
+
+
+def _ip_fit_embeds(ip_kwargs, solver):
+    """--ip_embeds as the solver's adapter reads it: a Linear adapter takes pooled embeds ([E], [B, E] or [B, 1, E] -> [B, E]); a
+    Resampler ("plus") adapter takes hidden states ([S, E] -> one row [1, S, E], or [B, S, E])"""
+    emb = ip_kwargs.get("ip_adapter_image_embeds")
+    if emb is None:
+        return ip_kwargs
+    adapter = getattr(getattr(solver, "engine", None), "ip_adapter", None)
+    if adapter is not None and getattr(adapter, "seq_input", False):
+        if emb.dim() not in (2, 3):
+            raise SystemExit(f"--ip_embeds: shape {tuple(emb.shape)}; a plus (Resampler) adapter takes [S, E] or [B, S, E] hidden states")
+        emb = emb[None] if emb.dim() == 2 else emb
+    else:
+        emb = emb.reshape(-1, emb.shape[-1])
+    return dict(ip_kwargs, ip_adapter_image_embeds=emb)
 
 
 def _control_kwargs(args, solver):

@@ -12,8 +12,9 @@ extern "C" {
 #endif
 
 /* ---- IP-Adapter: image prompts (diffusers `load_ip_adapter` with ip-adapter_sd15 / ip-adapter_sdxl / ip-adapter_sdxl_vit-h: one
- * adapter, the Linear + LayerNorm ImageProjection; not the Resampler "plus" or FaceID variants).  No reference counterpart: the
- * reference conditions on text only. */
+ * adapter, the Linear + LayerNorm ImageProjection; the Resampler "plus" variants load through the same cfgpp_unet_ip_load and take
+ * their image context through include/cfgpp_ip_plus.h; not the FaceID variants).  No reference counterpart: the reference conditions
+ * on text only. */
 
 /* Load one adapter tensor into a FINALIZED UNet engine (not a ControlNet), converted to the engine's dtypes and uploaded; `host`,
  * dtype, shape as cfgpp_unet_load_tensor.  Keys (cross = cross_attention_dim):
