@@ -175,11 +175,21 @@ int cfgpp_op_conv_out_ex(const void* x, void* out, int out_is_half, const void* 
                          int R, int H, int W, int C, int Cout, float post_scale, float post_shift, int clamp01, void* stream);
 /* A/B switch: 1 (default) conv_out on maps of >= 128 x 128 pixels runs the LDS-tiled kernel, 0 the wave-per-pixel kernel */
 void cfgpp_conv_out_set_tiled(int on);
+/* test hook: what the last cfgpp_op_conv_out / cfgpp_op_conv_out_ex call dispatched, a host-side record zeroed at entry (a refused
+ * call reports zeros): out4 = {kernel (0 wave per pixel, 1 LDS-tiled), CO of the instance (3, 4 or 8), out_is_half, workgroups} */
+void cfgpp_conv_out_last_launch(int* out4);
 int cfgpp_op_sinusoid(const float* vals, float scalar, float* out, int count, int dim, int out_ld, int out_off,
                       void* stream);
+/* out[m][n] = act_out(sum_k act_in(x[m][k]) W[n][k] + bias[n] + addend[m][n]); x fp32 with row stride ldx (0: one row for every
+ * m), read in 16-byte units: x 16-byte aligned, K % 8 == 0 and ldx % 4 == 0 (refused otherwise); W [N][K] fp16; out fp32, row
+ * stride ldo >= N, columns [N, ldo) untouched; bias / addend may be NULL */
 int cfgpp_op_skinny_gemm(const float* x, int ldx, const void* w, const float* bias, const float* addend, int add_ld,
                          float* out, int ldo, int M, int N, int K, int silu_in, int silu_out, void* stream);
+/* out[r][out_off + c] = float(in[r][c]), in [rows][cols] fp16 dense; refused: a null pointer, rows or cols <= 0, out_ld < out_off + cols */
 int cfgpp_op_f16_to_f32_rows(const void* in, float* out, int rows, int cols, int out_ld, int out_off, void* stream);
+/* the fan-out that ends the shared CFG prefix, alone: rows [0, h) of each p[k] ([>= 2h][row_elems[k]] fp16, 16-byte aligned,
+ * row_elems[k] % 8 == 0) are copied onto rows [h, 2h); nseg <= 3.  p / row_elems: HOST arrays. */
+int cfgpp_op_fanout_rows(void* const* p, const long* row_elems, int nseg, int h, void* stream);
 
 /* Generic implicit GEMM (conv3x3 / conv1x1 / linear), see cfgpp_amd/csrc/igemm.h.
  * a0/a1: activation sources (C0/C1 channels), amode 0 linear rows, 1 halo-padded NHWC,

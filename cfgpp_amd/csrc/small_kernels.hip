@@ -447,6 +447,11 @@ int cfgpp_op_conv_out_ex(const void* x, void* out, int out_is_half, const void* 
                          int R, int H, int W, int C, int Cout, float post_scale, float post_shift, int clamp01, void* stream);
 static int g_conv_out_tiled = 1;      // A/B switch: 0 = always the wave-per-pixel kernel
 void cfgpp_conv_out_set_tiled(int on) { g_conv_out_tiled = on ? 1 : 0; }
+static int g_conv_out_last[4] = {0, 0, 0, 0};      // kernel (0 wave per pixel, 1 tiled), CO of the instance, out_is_half, workgroups
+void cfgpp_conv_out_last_launch(int* out4) { for (int i = 0; i < 4; ++i) out4[i] = g_conv_out_last[i]; }
+static void conv_out_record(int kernel, int co, int out_is_half, unsigned blocks) {
+    g_conv_out_last[0] = kernel; g_conv_out_last[1] = co; g_conv_out_last[2] = out_is_half ? 1 : 0; g_conv_out_last[3] = (int)blocks;
+}
 
 int cfgpp_op_conv_out(const void* x, void* out, int out_is_half, const void* w, const float* bias,
                       int R, int H, int W, int C, int Cout, void* stream) {
@@ -458,13 +463,16 @@ int cfgpp_op_conv_out(const void* x, void* out, int out_is_half, const void* w, 
 // reference's two separate fp32 ops bit for bit)
 int cfgpp_op_conv_out_ex(const void* x, void* out, int out_is_half, const void* w, const float* bias,
                          int R, int H, int W, int C, int Cout, float post_scale, float post_shift, int clamp01, void* stream) {
-    CFGPP_REQUIRE(Cout >= 1 && Cout <= 8 && C % 8 == 0, "conv_out: Cout=%d C=%d", Cout, C);
+    conv_out_record(0, 0, 0, 0);
+    CFGPP_REQUIRE(Cout >= 1 && Cout <= 8 && C > 0 && C % 8 == 0, "conv_out: Cout=%d C=%d", Cout, C);
     CFGPP_REQUIRE(x && out && w, "conv_out: null pointer");
+    CFGPP_REQUIRE(R > 0 && H > 0 && W > 0, "conv_out: R=%d H=%d W=%d", R, H, W);
     const long total = (long)R * H * W;
     dim3 grid(cdiv(total, 4));
     hipStream_t s = (hipStream_t)stream;
     if (Cout <= 4 && C % 64 == 0 && (long)H * W >= 128 * 128 && g_conv_out_tiled) {      // large maps (VAE decoder): the LDS-tiled kernel
         dim3 tg((unsigned)((long)R * cdiv(H, 8) * cdiv(W, 32)));
+        conv_out_record(1, out_is_half || Cout > 3 ? 4 : 3, out_is_half, tg.x);
         if (out_is_half)
             hipLaunchKernelGGL((conv_out_tile_kernel<4, half_t>), tg, dim3(256), 0, s, (const half_t*)x, (half_t*)out, (const half_t*)w, bias, R, H, W, C, Cout, post_scale, post_shift, clamp01);
         else if (Cout <= 3)
@@ -476,11 +484,15 @@ int cfgpp_op_conv_out_ex(const void* x, void* out, int out_is_half, const void* 
     }
     if (Cout > 4) {       // VAE encoder moments (8 channels); weights must hold 8 output rows
         CFGPP_REQUIRE(!out_is_half, "conv_out: 8-channel output is fp32 only");
+        conv_out_record(0, 8, 0, grid.x);
         hipLaunchKernelGGL((conv_out_kernel<8, float>), grid, dim3(256), 0, s, (const half_t*)x, (float*)out, (const half_t*)w, bias, R, H, W, C, Cout, post_scale, post_shift, clamp01);
-    } else if (out_is_half)
+    } else if (out_is_half) {
+        conv_out_record(0, 4, 1, grid.x);
         hipLaunchKernelGGL((conv_out_kernel<4, half_t>), grid, dim3(256), 0, s, (const half_t*)x, (half_t*)out, (const half_t*)w, bias, R, H, W, C, Cout, post_scale, post_shift, clamp01);
-    else
+    } else {
+        conv_out_record(0, 4, 0, grid.x);
         hipLaunchKernelGGL((conv_out_kernel<4, float>), grid, dim3(256), 0, s, (const half_t*)x, (float*)out, (const half_t*)w, bias, R, H, W, C, Cout, post_scale, post_shift, clamp01);
+    }
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
 }
@@ -495,7 +507,8 @@ int cfgpp_op_sinusoid(const float* vals, float scalar, float* out, int count, in
 
 int cfgpp_op_skinny_gemm(const float* x, int ldx, const void* w, const float* bias, const float* addend, int add_ld,
                          float* out, int ldo, int M, int N, int K, int silu_in, int silu_out, void* stream) {
-    CFGPP_REQUIRE(x && w && out && M > 0 && N > 0 && K % 8 == 0, "skinny_gemm: bad args (K=%d)", K);
+    CFGPP_REQUIRE(x && w && out && M > 0 && N > 0 && K > 0 && K % 8 == 0, "skinny_gemm: bad args (M=%d N=%d K=%d)", M, N, K);
+    CFGPP_REQUIRE(ldx % 4 == 0, "skinny_gemm: ldx=%d must be a multiple of 4 (16-byte loads of x)", ldx);
     hipStream_t s = (hipStream_t)stream;
     if (M == 1) {
         dim3 grid(cdiv(N, 4 * 2), 1);
@@ -509,10 +522,18 @@ int cfgpp_op_skinny_gemm(const float* x, int ldx, const void* w, const float* bi
 }
 
 int cfgpp_op_f16_to_f32_rows(const void* in, float* out, int rows, int cols, int out_ld, int out_off, void* stream) {
+    CFGPP_REQUIRE(in && out, "f16_to_f32_rows: null pointer");
+    CFGPP_REQUIRE(rows > 0 && cols > 0 && out_off >= 0 && out_ld >= out_off + cols, "f16_to_f32_rows: rows=%d cols=%d out_ld=%d out_off=%d",
+                  rows, cols, out_ld, out_off);
     hipLaunchKernelGGL(f16_to_f32_rows_kernel, dim3(cdiv((long)rows * cols, 256) > 1024 ? 1024 : cdiv((long)rows * cols, 256)),
                        dim3(256), 0, (hipStream_t)stream, (const half_t*)in, out, rows, cols, out_ld, out_off);
     CFGPP_HIP_CHECK(hipGetLastError());
     return 0;
+}
+
+// the fan-out of the shared CFG prefix on its own (fanout_rows_launch above): p / row_elems are HOST arrays of nseg entries
+int cfgpp_op_fanout_rows(void* const* p, const long* row_elems, int nseg, int h, void* stream) {
+    return fanout_rows_launch(reinterpret_cast<half_t* const*>(p), row_elems, nseg, h, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -289,3 +289,91 @@ def err_stats(got: torch.Tensor, ref: torch.Tensor) -> dict:
     diff = (g - r)
     return dict(rel_l2=float(diff.norm() / (r.norm() + 1e-30)), max_abs=float(diff.abs().max()),
                 ref_max=float(r.abs().max()), finite=bool(torch.isfinite(g).all()))
+
+
+# ---- small kernels (csrc/small_kernels.hip), every argument of the C entry points; `out=`: a contiguous device tensor to write into
+# (tests that watch what the kernel leaves untouched) ---------------------------------------------------------------------------------
+def _dst(out, shape, dtype):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=DEV)
+    assert out.is_contiguous() and out.dtype == dtype and tuple(out.shape) == tuple(shape), (tuple(out.shape), shape, out.dtype)
+    return out
+
+
+def conv_in_add(z, wk, bias, R, Cout, cond=None, addend=None, out=None):
+    """z [zB, Cz, H, W] fp32 / fp16, wk [9 * Cin, Cout] fp32, cond [cond_rows, Cc, H, W] fp16, addend [add_rows, H+2, W+2, Cout] fp16"""
+    zB, Cz, H, W = z.shape
+    o = empty_pn(R, H, W, Cout) if out is None else _dst(out, (R, H + 2, W + 2, Cout), torch.float16)
+    check(lib().cfgpp_op_conv_in_add(P(z), int(z.dtype == torch.float16), P(cond), 0 if cond is None else cond.shape[0],
+                                     0 if cond is None else cond.shape[1], P(addend), 0 if addend is None else addend.shape[0], P(o), P(wk),
+                                     P(bias), R, zB, Cz, H, W, Cout, stream()), "cfgpp_op_conv_in_add")
+    return o
+
+
+def conv_in_ex(z, wk, bias, R, Cout, pre_w=None, pre_b=None, in_scale=1.0, out=None):
+    zB, Cz, H, W = z.shape
+    o = empty_pn(R, H, W, Cout) if out is None else _dst(out, (R, H + 2, W + 2, Cout), torch.float16)
+    check(lib().cfgpp_op_conv_in_ex(P(z), int(z.dtype == torch.float16), P(o), P(wk), P(bias), R, zB, Cz, H, W, Cout, P(pre_w), P(pre_b),
+                                    float(in_scale), stream()), "cfgpp_op_conv_in_ex")
+    return o
+
+
+def conv_out_ex(x_pn, wk, bias, out_half=True, post_scale=1.0, post_shift=0.0, clamp01=0, out=None):
+    """x_pn halo-padded NHWC fp16, wk [Cout, 9, C] fp16 -> NCHW [R, Cout, H, W]"""
+    R, Hp, Wp, C = x_pn.shape
+    H, W, Co = Hp - 2, Wp - 2, wk.shape[0]
+    o = _dst(out, (R, Co, H, W), torch.float16 if out_half else torch.float32)
+    check(lib().cfgpp_op_conv_out_ex(P(x_pn), P(o), int(out_half), P(wk), P(bias), R, H, W, C, Co, float(post_scale), float(post_shift),
+                                     int(clamp01), stream()), "cfgpp_op_conv_out_ex")
+    return o
+
+
+def conv_out_last_launch():
+    """(kernel 0 wave per pixel / 1 tiled, CO, out_is_half, workgroups) of the last conv_out call (cfgpp_debug.h)"""
+    return _last_launch("cfgpp_conv_out_last_launch", 4)
+
+
+def sinusoid_ex(vals, dim, count=None, scalar=0.0, out_ld=None, out_off=0, out=None):
+    """vals: device fp32 tensor or None (the scalar form: `count` rows of `scalar`); out [count, out_ld] fp32"""
+    count = vals.numel() if count is None else count
+    ld = dim if out_ld is None else out_ld
+    o = _dst(out, (count, ld), torch.float32)
+    check(lib().cfgpp_op_sinusoid(P(vals), float(scalar), P(o), count, dim, ld, out_off, stream()), "cfgpp_op_sinusoid")
+    return o
+
+
+def skinny_ex(x, ldx, w, bias, M, addend=None, add_ld=0, ldo=None, silu_in=False, silu_out=False, out=None):
+    """x: fp32 device tensor read as rows of stride ldx (0: one row), w [N, K] fp16; out [M, ldo] fp32"""
+    N, K = w.shape
+    ldo = N if ldo is None else ldo
+    o = _dst(out, (M, ldo), torch.float32)
+    check(lib().cfgpp_op_skinny_gemm(P(x), ldx, P(w), P(bias), P(addend), add_ld, P(o), ldo, M, N, K, int(silu_in), int(silu_out), stream()),
+          "cfgpp_op_skinny_gemm")
+    return o
+
+
+def f16_to_f32_rows(x, out_ld=None, out_off=0, out=None):
+    rows, cols = x.shape
+    ld = cols if out_ld is None else out_ld
+    o = _dst(out, (rows, ld), torch.float32)
+    check(lib().cfgpp_op_f16_to_f32_rows(P(x), P(o), rows, cols, ld, out_off, stream()), "cfgpp_op_f16_to_f32_rows")
+    return o
+
+
+def fanout_rows(bufs, h, row_elems=None, ptrs=None):
+    """rows [0, h) of every fp16 device tensor in bufs ([>= 2h, row_elems]) copied onto rows [h, 2h), in place, one launch"""
+    import ctypes
+    n = len(bufs)
+    p = (ctypes.c_void_p * n)(*(ptrs if ptrs is not None else [b.data_ptr() for b in bufs]))
+    e = (ctypes.c_long * n)(*(row_elems if row_elems is not None else [b.shape[1] for b in bufs]))
+    check(lib().cfgpp_op_fanout_rows(p, e, n, h, stream()), "cfgpp_op_fanout_rows")
+    return bufs
+
+
+def vae_posterior(conv_out, qw, qb, noise, scale, moments=True, out=None, out_moments=None):
+    """conv_out [B, 8, HW] fp32 -> (z [B, 4, HW], moments [B, 8, HW] or None)"""
+    B, _, HW = conv_out.shape
+    z = _dst(out, (B, 4, HW), torch.float32)
+    m = _dst(out_moments, (B, 8, HW), torch.float32) if moments else None
+    check(lib().cfgpp_op_vae_posterior(P(conv_out), P(qw), P(qb), P(noise), P(z), P(m), B, HW, float(scale), stream()), "cfgpp_op_vae_posterior")
+    return z, m
