@@ -109,8 +109,18 @@ VPRED_PROTOTYPES = {
     "cfgpp_cfg_rescale": (_I, [_P, _P, _F, _F, _P, _I, _L, _P]),
 }
 
+# the LCM extension header (include/cfgpp_lcm.h): Philox normals and the fused consistency step
+_U, _S = C.c_uint, C.POINTER(C.c_ulonglong)
+LCM_PROTOTYPES = {
+    "cfgpp_philox_normal": (_I, [_P, _I, _S, _I, _L, _U, _U, _P]),
+    "cfgpp_step_lcm": (_I, [_P, _P, _P, _P, _F, C.POINTER(C.c_float), _I, _I, _P, _S, _I, _L, _U, _P]),
+    "cfgpp_unet_set_time_cond": (_I, [_P, _I]),
+    "cfgpp_unet_guidance_embedding": (_I, [_P, C.POINTER(C.c_float), _P]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
+    "cfgpp_op_philox_raw": (_I, [_P, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _L, _P]),
     "cfgpp_op_softmax_rows": (_I, [_P, _L, _I, _P]),
     "cfgpp_op_conv_in_ex": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _F, _P]),
     "cfgpp_op_groupnorm": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
@@ -211,7 +221,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -131,6 +131,14 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
         shaped = unet_config_from_json(uconf, kw.get("unet_config") or _default_unet_config(sdxl))
         if shaped is not None:          # an SD2.x UNet, or another head count / context width / projection kind than the family's
             kw["unet_config"] = shaped
+        tdim = int(uconf.get("time_cond_proj_dim") or 0)
+        if tdim:                        # a guidance-embedded (LCM-distilled) UNet: time_embedding.cond_proj (cfgpp_amd/lcm.py)
+            from dataclasses import replace
+            from .unet_config import SD15_LCM, SDXL_LCM
+            base = kw.get("unet_config") or _default_unet_config(sdxl)
+            cand = replace(base, time_cond_proj_dim=tdim)
+            named = SDXL_LCM if sdxl else SD15_LCM
+            kw["unet_config"] = named if replace(cand, name=named.name) == named else replace(cand, name=base.name + "_lcm")
     # what the UNet predicts and the schedule it was trained on: only what differs from the reference's models is passed on, so a
     # plain SD1.5 / SDXL directory yields the keyword arguments it always did
     scfg = os.path.join(d, "scheduler", "scheduler_config.json")
@@ -145,6 +153,10 @@ def solver_kwargs_from_dir(model_dir, sdxl: bool, device="cuda", vae_dir=None, t
             kw["zero_terminal_snr"] = True
         if sconf.get("timestep_spacing") == "trailing":
             kw["timestep_spacing"] = "trailing"
+        if sconf.get("_class_name") == "LCMScheduler":      # the `lcm` solvers' schedule (cfgpp_amd/lcm.py); other solvers ignore the keys
+            kw["lcm_original_steps"] = int(sconf.get("original_inference_steps", 50))
+            kw["timestep_scaling"] = float(sconf.get("timestep_scaling", 10.0))
+            kw.pop("timestep_spacing", None)                # LCMScheduler's own timesteps: its "leading" default is not DDIM's
     pad_token = _pad_token(os.path.join(d, "tokenizer", "special_tokens_map.json"))
     if pad_token is not None:
         kw["pad_token"] = pad_token             # SD2.x pads with "!" (the solvers ignore the key; the text tower below takes it)

@@ -45,7 +45,7 @@ def controlnet_param_shapes(cfg: UNetConfig, embed_channels: Tuple[int, ...] = E
     the conditioning embedding and the zero convolutions."""
     P: "OrderedDict[str, tuple]" = OrderedDict()
     for k, s in param_shapes(cfg).items():
-        if k.startswith(("up_blocks.", "conv_norm_out.", "conv_out.")):
+        if k.startswith(("up_blocks.", "conv_norm_out.", "conv_out.", "time_embedding.cond_proj.")):     # (a ControlNet has no guidance embedding)
             continue
         P[k] = s
 

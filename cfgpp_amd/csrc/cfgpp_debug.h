@@ -159,6 +159,11 @@ void cfgpp_freeu_last_launch(int* out5);
  * refusals as cfgpp_unet_lora.  Synchronises the device. */
 int cfgpp_unet_read_weight(cfgpp_unet* u, const char* key, void* host_fp16_out);
 
+/* the raw words of the LCM noise generator (include/cfgpp_lcm.h; csrc/lcm_kernels.hip): out [n][4] uint32 on the device, 16-byte
+ * aligned, out[i] = Philox4x32-10 of counter (ctr_host4[0] + i mod 2^32, ctr_host4[1], ctr_host4[2], ctr_host4[3]) under key
+ * (key_host2[0], key_host2[1]); both arrays are host memory, read before the call returns.  1 <= n <= 2^24. */
+int cfgpp_op_philox_raw(void* out, const unsigned* ctr_host4, const unsigned* key_host2, long n, void* stream);
+
 /* per-launch timing of the VAE decoder (a diagnostic: scripts and HipVAE.profile; the UNet's twin cfgpp_unet_profile feeds the
  * benchmark and stays in include/cfgpp.h): one decode (image post-processing included) with a HIP event between every launch of the decoder plan; `detail` receives one
  * line per launch: index \t family (0 igemm, 1 attention GEMMs, 2 norm / softmax, 3 small) \t description \t us \t GFLOP */

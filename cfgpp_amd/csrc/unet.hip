@@ -11,6 +11,7 @@
 // buffers in halo-padded NHWC fp16 - no allocation, no host sync, one stream.
 #include "engine_base.h"
 #include "../../include/cfgpp_ip_plus.h"
+#include "../../include/cfgpp_lcm.h"
 #include "freeu.h"
 
 struct cfgpp_unet : EngineBase {
@@ -67,6 +68,14 @@ struct cfgpp_unet : EngineBase {
     float* d_sin_t = nullptr; float* d_emb_h = nullptr; float* d_emb_t = nullptr; float* d_emb = nullptr;
     float* d_temb_all = nullptr; int temb_total = 0;
     float* d_add_in = nullptr; float* d_add_h = nullptr; float* d_aug = nullptr;
+    // guidance-embedded UNets (include/cfgpp_lcm.h: cfgpp_unet_set_time_cond, before finalize): time_cond = time_cond_proj_dim.
+    // cfgpp_unet_guidance_embedding computes, once per job, d_time_add = linear_1.weight x (cond_proj x w_emb) into an engine-owned
+    // buffer whose address never changes; the forward's linear_1 launch takes it as its addend (it lands before the SiLU), so
+    // linear_1(sinusoid(t) + cond_proj(w_emb)) costs the forward no launch of its own.
+    int time_cond = 0; bool time_cond_set = false;
+    half_t* w_cond = nullptr; half_t* w_time1 = nullptr;
+    float* d_w_emb = nullptr; float* d_cond_vec = nullptr; float* d_time_add = nullptr;
+    std::vector<float> h_w_emb;             // the host copy the upload reads (stable address)
 
     // transformer scratch (token-major)
     half_t *tok_x = nullptr, *tok_ln = nullptr, *tok_attn = nullptr, *tok_ff = nullptr;
@@ -489,8 +498,20 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
         half_t* w1 = B.linear("time_embedding.linear_1.weight"); float* b1 = B.f32("time_embedding.linear_1.bias");
         half_t* w2 = B.linear("time_embedding.linear_2.weight"); float* b2 = B.f32("time_embedding.linear_2.bias");
         cfgpp_unet* uu = u;
+        const float* time_add = nullptr;        // guidance-embedded UNets: linear_1.weight x cond_proj(w_emb), added before the SiLU
+        if (u->time_cond) {
+            u->w_time1 = w1;
+            u->w_cond = B.linear("time_embedding.cond_proj.weight");
+            u->d_w_emb = (float*)u->dmalloc((size_t)u->time_cond * sizeof(float));
+            u->d_cond_vec = (float*)u->dmalloc((size_t)c0 * sizeof(float));
+            u->d_time_add = (float*)u->dmalloc((size_t)temb_dim * sizeof(float));
+            CFGPP_REQUIRE(u->w_cond && u->d_w_emb && u->d_cond_vec && u->d_time_add, "finalize: time_embedding.cond_proj: %s",
+                          B.ok ? "hipMalloc failed" : B.err.c_str());
+            u->h_w_emb.assign((size_t)u->time_cond, 0.f);
+            time_add = u->d_time_add;
+        }
         u->plan.push_back([=](hipStream_t s, int) { return cfgpp_op_sinusoid(uu->in_t_dev, uu->in_t, uu->d_sin_t, 1, c0, c0, 0, s); });
-        u->plan.push_back([=](hipStream_t s, int) { return cfgpp_op_skinny_gemm(uu->d_sin_t, c0, w1, b1, nullptr, 0, uu->d_emb_h, temb_dim, 1, temb_dim, c0, 0, 1, s); });
+        u->plan.push_back([=](hipStream_t s, int) { return cfgpp_op_skinny_gemm(uu->d_sin_t, c0, w1, b1, time_add, 0, uu->d_emb_h, temb_dim, 1, temb_dim, c0, 0, 1, s); });
         if (per_row_temb) {
             // emb[r] = linear_2(h) + aug[r or 0]
             u->plan.push_back([=](hipStream_t s, int rows) {
@@ -850,6 +871,36 @@ int cfgpp_unet_set_max_tokens(cfgpp_unet* u, int max_tokens) {
     CFGPP_REQUIRE(max_tokens == 77 || max_tokens == 154 || max_tokens == 231 || max_tokens == 308,
                   "set_max_tokens: max_tokens=%d (77, 154, 231 or 308)", max_tokens);
     u->max_tokens = max_tokens;
+    return 0;
+}
+
+// guidance-embedded UNets (LCM distillations; include/cfgpp_lcm.h): the extra parameter time_embedding.cond_proj.weight [c0][dim]
+int cfgpp_unet_set_time_cond(cfgpp_unet* u, int dim) {
+    CFGPP_REQUIRE(u, "set_time_cond: null engine");
+    CFGPP_REQUIRE(!u->finalized, "set_time_cond: time_cond_proj_dim=%d after cfgpp_unet_finalize (the parameter table is fixed there)", dim);
+    CFGPP_REQUIRE(!u->control, "set_time_cond: a ControlNet-mode engine (out_channels = 0) has no guidance embedding");
+    CFGPP_REQUIRE(u->time_cond == 0, "set_time_cond: already set (time_cond_proj_dim=%d)", u->time_cond);
+    CFGPP_REQUIRE(dim >= 8 && dim % 8 == 0 && dim <= 4096, "set_time_cond: time_cond_proj_dim=%d (a multiple of 8 in 8 .. 4096)", dim);
+    expect_linear(u, "time_embedding.cond_proj", u->cfg.block_out_channels[0], dim, false);
+    u->time_cond = dim;
+    return 0;
+}
+
+// once per job: d_time_add = linear_1.weight x (cond_proj.weight x w_emb), two skinny-GEMM launches on `stream`
+int cfgpp_unet_guidance_embedding(cfgpp_unet* u, const float* w_emb_host, void* stream) {
+    CFGPP_REQUIRE(u && u->finalized, "guidance_embedding: the engine is not finalized");
+    CFGPP_REQUIRE(u->time_cond > 0, "guidance_embedding: this UNet has no time_embedding.cond_proj (cfgpp_unet_set_time_cond before finalize)");
+    CFGPP_REQUIRE(w_emb_host, "guidance_embedding: null embedding");
+    const int dim = u->time_cond, c0 = u->cfg.block_out_channels[0], temb_dim = 4 * c0;
+    for (int i = 0; i < dim; ++i) CFGPP_REQUIRE(std::isfinite(w_emb_host[i]), "guidance_embedding: w_emb[%d] is not finite", i);
+    hipStream_t s = (hipStream_t)stream;
+    std::memcpy(u->h_w_emb.data(), w_emb_host, (size_t)dim * sizeof(float));
+    CFGPP_HIP_CHECK(hipMemcpyAsync(u->d_w_emb, u->h_w_emb.data(), (size_t)dim * sizeof(float), hipMemcpyHostToDevice, s));
+    int e = cfgpp_op_skinny_gemm(u->d_w_emb, dim, u->w_cond, nullptr, nullptr, 0, u->d_cond_vec, c0, 1, c0, dim, 0, 0, s);
+    if (e) return e;
+    e = cfgpp_op_skinny_gemm(u->d_cond_vec, c0, u->w_time1, nullptr, nullptr, 0, u->d_time_add, temb_dim, 1, temb_dim, c0, 0, 0, s);
+    if (e) return e;
+    u->time_cond_set = true;
     return 0;
 }
 
@@ -1315,6 +1366,8 @@ int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
                        void* stream) {
     CFGPP_REQUIRE(u && u->finalized, "forward: context not finalized");
     CFGPP_REQUIRE(u->ctx_set, "forward: set_context has not been called");
+    CFGPP_REQUIRE(!u->time_cond || u->time_cond_set, "forward: a guidance-embedded UNet (time_cond_proj_dim=%d) needs "
+                  "cfgpp_unet_guidance_embedding first", u->time_cond);
     CFGPP_REQUIRE(z && eps_out && z_rows > 0 && rows > 0 && rows <= u->cfg.max_rows, "forward: bad args (rows=%d max=%d)", rows, u->cfg.max_rows);
     CFGPP_REQUIRE(rows == u->ctx_rows, "forward: rows=%d but context was set for %d rows", rows, u->ctx_rows);
     CFGPP_REQUIRE(u->control || u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
@@ -1355,6 +1408,8 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
                             int renoise_uc, void* stream) {
     CFGPP_REQUIRE(u && u->finalized && u->ctx_set, "sample_graph: context not ready");
     CFGPP_REQUIRE(z && z0t && eps && eps_uc && eps_c && host_steps && n_steps > 0 && z_rows > 0, "sample_graph: bad args");
+    CFGPP_REQUIRE(!u->time_cond || u->time_cond_set, "sample_graph: a guidance-embedded UNet (time_cond_proj_dim=%d) needs "
+                  "cfgpp_unet_guidance_embedding first", u->time_cond);
     CFGPP_REQUIRE(rows == u->ctx_rows && rows <= u->cfg.max_rows, "sample_graph: rows=%d but context was set for %d rows", rows, u->ctx_rows);
     CFGPP_REQUIRE(!u->ctrl && !u->control, "sample_graph: a ControlNet is attached (a controlled step is not captured): detach it "
                                             "(cfgpp_unet_attach_control(u, NULL, 0)) or run the eager loop");
@@ -1446,6 +1501,8 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
                        void* stream, double* out_ms, double* out_flops, int* out_launches, char* detail, long detail_cap) {
     CFGPP_REQUIRE(u && u->finalized && u->ctx_set, "profile: context not ready");
     CFGPP_REQUIRE(z && eps_out && out_ms && out_flops && out_launches && rows == u->ctx_rows, "profile: bad args");
+    CFGPP_REQUIRE(!u->time_cond || u->time_cond_set, "profile: a guidance-embedded UNet (time_cond_proj_dim=%d) needs "
+                  "cfgpp_unet_guidance_embedding first", u->time_cond);
     CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "profile: the image context (IP-Adapter) was set for %d rows", u->ip_rows);
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->out_eps = eps_out;
     hipStream_t s = (hipStream_t)stream;

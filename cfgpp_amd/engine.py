@@ -206,6 +206,63 @@ def cfg_rescale(v_uc: torch.Tensor, v_c: torch.Tensor, lam: float, phi: float, r
 
 
 # ----------------------------------------------------------------------------
+# LCM (include/cfgpp_lcm.h)
+# ----------------------------------------------------------------------------
+def _seed_array(seeds, B: int, who: str):
+    if len(seeds) != B:
+        raise CfgppError(f"{who}: {len(seeds)} seeds for {B} chains")
+    return (C.c_ulonglong * B)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
+
+
+def philox_normal(out: torch.Tensor, seeds, draw: int, stream_id: int) -> torch.Tensor:
+    """fill ``out`` [B, ...] (fp32 or fp16) with the seeded normals of cfgpp_philox_normal: chain b's row from ``seeds[b]``, draw index
+    ``draw``, ``stream_id`` 0 (LCM renoise) / 1 (ancestral noise)"""
+    lib = _lib.load()
+    _require_cuda(out, "out")
+    if out.dtype not in (torch.float16, torch.float32) or out.dim() < 2:
+        raise CfgppError("philox_normal: out must be fp32 or fp16 [B, ...]")
+    B = int(out.shape[0])
+    check(lib.cfgpp_philox_normal(out.data_ptr(), 1 if out.dtype == torch.float16 else 0, _seed_array(seeds, B, "philox_normal"), B,
+                                  out.numel() // B, int(draw), int(stream_id), _stream_ptr(out)), "cfgpp_philox_normal")
+    return out
+
+
+def step_lcm(z: torch.Tensor, den_out: torch.Tensor, m_uc: torch.Tensor, m_c: torch.Tensor, lam: float, coef6, pred_v: bool, last: bool,
+             seeds=None, draw: int = 0, noise: Optional[torch.Tensor] = None):
+    """one fused LCM step in place on the fp32 latent ``z`` [B, ...] (cfgpp_step_lcm); ``coef6`` from ``lcm.step_coeffs``; the
+    renoising noise is ``noise`` (fp32, z's shape) or, with None, drawn in the kernel from ``seeds`` / ``draw``"""
+    lib = _lib.load()
+    for n, t in (("z", z), ("den_out", den_out), ("m_uc", m_uc), ("m_c", m_c)) + ((("noise", noise),) if noise is not None else ()):
+        _require_cuda(t, n)
+        if t.numel() != z.numel():
+            raise CfgppError("step_lcm: size mismatch")
+    if z.dtype != torch.float32 or den_out.dtype != torch.float32 or (noise is not None and noise.dtype != torch.float32):
+        raise CfgppError("step_lcm: z, den_out and noise must be fp32")
+    if m_uc.dtype != torch.float16 or m_c.dtype != torch.float16:
+        raise CfgppError("step_lcm: the model output must be fp16")
+    if len(coef6) != 6:
+        raise CfgppError("step_lcm: coef6 = (c1 | s_v, c2 | a_z, c_out, c_skip, c3, c4)")
+    B = int(z.shape[0])
+    sd = None
+    if not last and noise is None:
+        if seeds is None:
+            raise CfgppError("step_lcm: a step that is not the last needs seeds or noise")
+        sd = _seed_array(seeds, B, "step_lcm")
+    arr = (C.c_float * 8)(*[float(v) for v in coef6], 0.0, 0.0)
+    check(lib.cfgpp_step_lcm(z.data_ptr(), den_out.data_ptr(), m_uc.data_ptr(), m_c.data_ptr(), float(lam), arr, int(bool(pred_v)),
+                             int(bool(last)), _ptr(noise), sd, B, z.numel() // B, int(draw), _stream_ptr(z)), "cfgpp_step_lcm")
+
+
+def philox_raw(ctr4, key2, n: int, device=None) -> torch.Tensor:
+    """test hook (cfgpp_debug.h: cfgpp_op_philox_raw): [n, 4] int32 holding the uint32 words of counters (ctr4[0] + i, ctr4[1..3])"""
+    lib = _lib.load()
+    out = torch.empty((int(n), 4), dtype=torch.int32, device=device or "cuda")
+    check(lib.cfgpp_op_philox_raw(out.data_ptr(), (C.c_uint * 4)(*[int(v) & 0xFFFFFFFF for v in ctr4]),
+                                  (C.c_uint * 2)(*[int(v) & 0xFFFFFFFF for v in key2]), int(n), _stream_ptr(out)), "cfgpp_op_philox_raw")
+    return out
+
+
+# ----------------------------------------------------------------------------
 # UNet engine
 # ----------------------------------------------------------------------------
 def unet_config_c(cfg: UNetConfig, H: int, W: int, max_rows: int, out_channels: Optional[int] = None) -> UNetConfigC:
@@ -255,8 +312,11 @@ class HipUNet:
         self.max_tokens = 77
         if int(max_tokens) != 77:
             self.set_max_tokens(max_tokens)
+        self.time_cond = 0                           # time_cond_proj_dim of a guidance-embedded UNet (include/cfgpp_lcm.h)
+        if int(getattr(cfg, "time_cond_proj_dim", 0)):
+            self.set_time_cond(cfg.time_cond_proj_dim)
         self.freeu = None                            # (s1, s2, b1, b2) while FreeU is on (set_freeu)
-        self.latent_channels = cfg.out_channels      # z carries these; an inpaint UNet's other inputs come from image_condition
+        self.latent_channels = cfg.out_channels     # z carries these; an inpaint UNet's other inputs come from image_condition
         self.cond_channels = cfg.in_channels - cfg.out_channels
 
     def __del__(self):
@@ -292,6 +352,20 @@ class HipUNet:
         """before ``finalize``: size the cross-attention buffers for contexts of up to ``max_tokens`` = 77, 154, 231 or 308 tokens"""
         check(self.lib.cfgpp_unet_set_max_tokens(self._h, int(max_tokens)), "cfgpp_unet_set_max_tokens")
         self.max_tokens = int(max_tokens)
+        return self
+
+    def set_time_cond(self, dim: int):
+        """before ``finalize``: the UNet has ``time_embedding.cond_proj`` [c0, dim] (include/cfgpp_lcm.h: cfgpp_unet_set_time_cond)"""
+        check(self.lib.cfgpp_unet_set_time_cond(self._h, int(dim)), "cfgpp_unet_set_time_cond")
+        self.time_cond = int(dim)
+        return self
+
+    def guidance_embedding(self, w_emb):
+        """once per job on a guidance-embedded UNet: ``w_emb`` [time_cond] (``lcm.guidance_scale_embedding``), host values"""
+        w = [float(v) for v in w_emb]
+        if len(w) != self.time_cond or not self.time_cond:
+            raise CfgppError(f"guidance_embedding: {len(w)} values for time_cond_proj_dim={self.time_cond}")
+        check(self.lib.cfgpp_unet_guidance_embedding(self._h, (C.c_float * len(w))(*w), _stream_ptr()), "cfgpp_unet_guidance_embedding")
         return self
 
     def finalize(self):

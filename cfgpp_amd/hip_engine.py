@@ -258,6 +258,19 @@ class HipEngine:
     step_ddim_v = staticmethod(E.step_ddim_v)
     v_to_eps = staticmethod(E.v_to_eps)
     cfg_rescale = staticmethod(E.cfg_rescale)
+    # LCM (include/cfgpp_lcm.h)
+    step_lcm = staticmethod(E.step_lcm)
+    philox_normal = staticmethod(E.philox_normal)
+
+    @property
+    def time_cond_proj_dim(self) -> int:
+        """width of the guidance-scale embedding of a guidance-embedded (LCM-distilled) UNet; 0: a plain UNet"""
+        return self.unet.time_cond
+
+    def set_guidance_embedding(self, w_emb):
+        """guidance-embedded UNets, once per job before ``predict``: the embedding of the job's guidance scale
+        (``lcm.guidance_scale_embedding``; include/cfgpp_lcm.h: cfgpp_unet_guidance_embedding)"""
+        self.unet.guidance_embedding(w_emb)
 
     def randn_like(self, x):
         """ancestral noise: device RNG, like the reference's torch.randn_like on the GPU"""

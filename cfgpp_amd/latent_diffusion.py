@@ -130,6 +130,13 @@ class StableDiffusion:
         self._job_rescale = None
         self._refuse_unsupported_prediction(zero_snr, spacing)
         self.guidance_rescale = self._check_guidance_rescale(kwargs.get("guidance_rescale") or 0.0)
+        # per-step noise of the ancestral solvers: "torch" (torch.randn_like, the reference's) or "philox" (seeded, in HIP: cfgpp_lcm.h)
+        self.noise = kwargs.get("noise") or "torch"
+        if self.noise not in ("torch", "philox"):
+            raise ValueError(f"noise={self.noise!r}: 'torch' or 'philox'")
+        if self.noise == "philox" and not self.ancestral:
+            raise ValueError(f"{self._name()}: noise='philox' is for the ancestral solvers (euler_a*, dpm++_2s_a*): no other solver "
+                             "draws per-step noise")
 
         # scheduler tables (host)
         self.tables = SchedulerTables(solver_config.num_sampling, self.scheduler_kind, zero_terminal_snr=zero_snr, timestep_spacing=spacing)
@@ -203,6 +210,7 @@ class StableDiffusion:
     # ------------------------------------------------------------------ v-prediction, zero terminal SNR, guidance rescale
     solver_name = None          # the registry name (registry.py)
     sigma_solver = False        # Karras-sigma (k-diffusion) loop: sigma_max of a zero-terminal-SNR schedule is infinite
+    ancestral = False           # draws fresh noise every step (euler_a*, dpm++_2s_a*): takes noise="philox"
     vpred_ok = True             # False: the solver's update has no v form (inpaint blend)
     rescale_ok = False          # True on `ddim` / `ddim_cfg++`: the text-to-image DDIM loops take guidance_rescale
 
@@ -520,6 +528,21 @@ class StableDiffusion:
             out.append(torch.randn((1,) + tuple(size[1:]), generator=g))
         return torch.cat(out, dim=0)
 
+    @staticmethod
+    def _chain_seeds(seeds, B: int, who: str) -> List[int]:
+        """the 64-bit seeds that key the chains' in-kernel noise (include/cfgpp_lcm.h): the caller's ``seeds`` - the ones that made the
+        start latent - or, with None, B values drawn once per job from torch's CPU generator.  A sharded run has to pass its rank's
+        seeds: ranks that draw their own would repeat each other's noise."""
+        if seeds is None:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise ValueError(f"{who} in a sharded run (world size > 1) needs seeds=[...] for this rank's chains: ranks that draw "
+                                 "their own seeds would repeat each other's noise")
+            return [int(v) for v in torch.randint(0, 2 ** 63 - 1, (int(B),), dtype=torch.int64)]
+        if len(seeds) != int(B):
+            raise ValueError(f"{len(seeds)} seeds for a batch of {B}")
+        return [int(s) for s in seeds]
+
     # ------------------------------------------------------------------ k-diffusion helpers
     def timestep(self, sigma):
         return self.tables.timestep(sigma)
@@ -666,6 +689,11 @@ class StableDiffusion:
         x = self._kdiff_start((B, self.cfg.out_channels) + self.latent_hw, sigmas, seeds)
         xc, den, uden = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
         x2, den2, uden2 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+        # noise="philox": the injected noise comes from the seeded counter-based generator (cfgpp_philox_normal, stream 1, draw =
+        # step) into one preallocated buffer - chain b of a batch then equals chain b alone; "torch" (default): randn_like, as ever
+        philox = self.noise == "philox"
+        if philox:
+            job_seeds, nbuf = self._chain_seeds(seeds, B, f"{self._name()} with noise='philox'"), torch.empty_like(x)
         variant = 1 if cfgpp else 0
         sem = self.scalar_semantics
         t_fn = lambda sg: sg.log().neg()       # noqa: E731
@@ -705,7 +733,8 @@ class StableDiffusion:
                 else:       # x = ratio * x - expm1(-h) * den_2
                     self.engine.lincomb(x, x, den2, None, ratio_n, first((-h).expm1()), 0)
             if sigmas[i + 1] > 0:
-                self.engine.lincomb(x, x, self.engine.randn_like(x), None, float(sigma_up), 0.0, 2)
+                noise = self.engine.philox_normal(nbuf, job_seeds, i, 1) if philox else self.engine.randn_like(x)
+                self.engine.lincomb(x, x, noise, None, float(sigma_up), 0.0, 2)
             if callback_fn is not None:
                 self._run_callback(callback_fn, i, new_t, den, x)
         return den, x
@@ -757,6 +786,7 @@ class EulerAncestralCFGSolver(StableDiffusion):
     """Karras Euler + ancestral sampling (reference: latent_diffusion.py:349-390)."""
     cfgpp, two_stage = False, False
     sigma_solver = True
+    ancestral = True
 
     @torch.no_grad()
     @controlled

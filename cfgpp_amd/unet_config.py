@@ -33,6 +33,7 @@ class UNetConfig:
     sample_size: int = 64          # default latent H = W
     vae_scale: float = 0.18215
     linear_projection: Optional[bool] = None    # transformer proj_in / proj_out as linear layers; None: linear iff addition_embed
+    time_cond_proj_dim: int = 0    # guidance-embedded (LCM-distilled) UNets: width of the guidance-scale embedding; 0: none
 
     @property
     def num_levels(self) -> int:
@@ -75,7 +76,15 @@ SD21_BASE = replace(SD21, name="sd21_base", sample_size=64)
 TINY_SD2 = UNetConfig(name="tiny_sd2", block_out_channels=(64, 128, 128), level_has_attn=(1, 1, 0), transformer_depth=(1, 1, 1),
                       num_heads=(1, 2, 2), cross_attention_dim=128, linear_projection=True, sample_size=12)
 
-CONFIGS = {c.name: c for c in (SD21, SD21_BASE, TINY_SD2, SD15, SDXL, TINY_SD, TINY_XL, SD15_INPAINT, SDXL_INPAINT, TINY_SD_INPAINT, TINY_XL_INPAINT)}
+# guidance-embedded UNets of the distilled LCM checkpoints (SimianLuo/LCM_Dreamshaper_v7, latent-consistency/lcm-sdxl): the base
+# topology plus time_embedding.cond_proj [c0, time_cond_proj_dim] (no bias), fed the embedding of the guidance scale
+SD15_LCM = replace(SD15, name="sd15_lcm", time_cond_proj_dim=256)
+SDXL_LCM = replace(SDXL, name="sdxl_lcm", time_cond_proj_dim=256)
+TINY_SD_LCM = replace(TINY_SD, name="tiny_sd_lcm", time_cond_proj_dim=32)
+TINY_XL_LCM = replace(TINY_XL, name="tiny_xl_lcm", time_cond_proj_dim=32)
+
+CONFIGS = {c.name: c for c in (SD21, SD21_BASE, TINY_SD2, SD15, SDXL, TINY_SD, TINY_XL, SD15_INPAINT, SDXL_INPAINT, TINY_SD_INPAINT, TINY_XL_INPAINT,
+                               SD15_LCM, SDXL_LCM, TINY_SD_LCM, TINY_XL_LCM)}
 INPAINT_OF = {"sd15": SD15_INPAINT, "sdxl": SDXL_INPAINT, "tiny_sd": TINY_SD_INPAINT, "tiny_xl": TINY_XL_INPAINT}
 
 
@@ -136,6 +145,8 @@ def param_shapes(cfg: UNetConfig) -> "OrderedDict[str, tuple]":
 
     conv("conv_in", c0, cfg.in_channels, 3)
     lin("time_embedding.linear_1", temb, c0)
+    if cfg.time_cond_proj_dim:
+        lin("time_embedding.cond_proj", c0, cfg.time_cond_proj_dim, False)
     lin("time_embedding.linear_2", temb, temb)
     if cfg.addition_embed:
         lin("add_embedding.linear_1", temb, 6 * cfg.addition_time_embed_dim + cfg.addition_pooled_dim)

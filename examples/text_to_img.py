@@ -62,6 +62,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--ip_adapter_dir", default=None, help="folder that holds the CLIP image tower (image_encoder/)")
     ap.add_argument("--ip_embeds", default=None, metavar="FILE.npy", help="precomputed CLIP image embeds [1 or batch, embed_dim]")
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
+    ap.add_argument("--lcm_original_steps", type=int, default=None,
+                    help="--method lcm: original_inference_steps of the LCM schedule (default: the checkpoint's scheduler_config.json, else 50)")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
     from cfgpp_amd import vpred
@@ -100,15 +102,20 @@ def main(argv=None, solver_kwargs=None) -> None:
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference
 
+    lcm = args.method == "lcm"      # the LCM sampler has its own registry (cfgpp_amd/lcm.py); --NFE, --cfg_guidance and --lora as ever
+    if lcm:
+        from cfgpp_amd.lcm import get_lcm_solver
+        if args.lcm_original_steps is not None:
+            kw["lcm_original_steps"] = args.lcm_original_steps
     if args.model in ("sdxl", "sdxl_lightning"):
         from cfgpp_amd.latent_sdxl import get_solver
-        solver = get_solver(args.method, **kw)
+        solver = get_lcm_solver("lcm", model="sdxl", **kw) if lcm else get_solver(args.method, **kw)
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
                                cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
                                **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
-        solver = get_solver(args.method, **kw)
+        solver = get_lcm_solver("lcm", model="sd15", **kw) if lcm else get_solver(args.method, **kw)
         result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
                                **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
 
