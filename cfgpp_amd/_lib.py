@@ -118,6 +118,16 @@ LCM_PROTOTYPES = {
     "cfgpp_unet_guidance_embedding": (_I, [_P, C.POINTER(C.c_float), _P]),
 }
 
+# the MultiDiffusion panorama extension header (include/cfgpp_panorama.h): the window gather and the fused view step
+class PanoViewsC(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("B", "C", "Hp", "Wp", "h", "w", "stride", "circular", "chunk_views")]
+
+
+PANORAMA_PROTOTYPES = {
+    "cfgpp_views_gather": (_I, [C.POINTER(PanoViewsC), _P, _P, _P]),
+    "cfgpp_step_ddim_views": (_I, [C.POINTER(PanoViewsC), _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _P]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_philox_raw": (_I, [_P, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _L, _P]),
@@ -221,7 +231,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -15,24 +15,11 @@
 // HBM-bound: per element 4 B z in + 2+2 B model out in + 4 B den out + 4 B z out = 16 B, cfgpp_step_ddim's traffic; the Philox
 // block + two logf / sincospif pairs per 4 elements ride under it (measured: profiles/lcm/README.md).
 #include "common.h"
+#include "step_math.h"
 #include "../../include/cfgpp_lcm.h"
 #include "cfgpp_debug.h"
 
 namespace {
-
-// the two helpers of step_kernels.hip, restated (that file keeps them private)
-__device__ __forceinline__ float h_round(float x) {
-    asm volatile("" : "+v"(x));
-    return (float)(half_t)x;
-}
-__device__ __forceinline__ float cfg_mix_h(float uc, float c, float lam) {
-    float d = h_round(__fsub_rn(c, uc));
-    float e = h_round(__fmul_rn(d, lam));
-    return h_round(__fadd_rn(uc, e));
-}
-__device__ __forceinline__ float div_as_ref(float x, float c) {
-    return c < 0.f ? __fmul_rn(x, -c) : __fdiv_rn(x, c);
-}
 
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u, PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;
 

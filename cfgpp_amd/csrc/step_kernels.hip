@@ -16,36 +16,12 @@
 //
 // HBM-bound: per element 4 B z in + 2+2 B eps in + 4 B z0t out + 4 B z out = 16 B.
 #include "common.h"
+#include "step_math.h"
 
 namespace {
 
-// RNE to fp16 of a value that has ALREADY been rounded to fp32 (torch computes the fp16 result of an
-// op in fp32 and then rounds: two roundings).  The empty asm makes the fp32 value opaque so the compiler
-// cannot fuse mul+convert into v_fma_mixlo_f16, which rounds the exact product ONCE and differs on ties.
-__device__ __forceinline__ float h_round(float x) {
-    asm volatile("" : "+v"(x));
-    return (float)(half_t)x;
-}
-
-// eps_hat = eps_uc + lam*(eps_c - eps_uc) with fp16 rounding after each op
-__device__ __forceinline__ float cfg_mix_h(float uc, float c, float lam) {
-    float d = h_round(__fsub_rn(c, uc));
-    float e = h_round(__fmul_rn(d, lam));
-    return h_round(__fadd_rn(uc, e));
-}
-__device__ __forceinline__ float cfg_mix_f(float uc, float c, float lam) {
-    return __fadd_rn(uc, __fmul_rn(__fsub_rn(c, uc), lam));
-}
-
-// `x / c` as the reference's backend evaluates it.  c > 0: IEEE division (torch-CPU, and every tensor / tensor division).
-// c < 0: the host passes c = -fl32(1 / divisor) and the kernel MULTIPLIES by -c: torch's GPU `div` with a CPU 0-dim
-// scalar (or python number) divisor - which is what `/ at.sqrt()`, `/ sigma.item()`, `/ (2*r)` and `/ (sigma**2+1)**0.5`
-// are in the reference - computes `a * (1/b)` with the reciprocal taken once on the host in fp32
-// (ATen BinaryDivTrueKernel.cu, `iter.is_cpu_scalar(2)`): up to 1 ulp away from the true quotient.  Every divisor on
-// this path is positive, so the sign is free to carry the choice (cfgpp_amd/coeffs.py: `divisor()`).
-__device__ __forceinline__ float div_as_ref(float x, float c) {
-    return c < 0.f ? __fmul_rn(x, -c) : __fdiv_rn(x, c);
-}
+// h_round, cfg_mix_h / cfg_mix_f, div_as_ref and the per-element update ddim_update_h: step_math.h (shared with the v-prediction,
+// LCM and panorama step kernels)
 
 template <bool EPS_HALF>
 __global__ void __launch_bounds__(256)
@@ -74,14 +50,15 @@ ddim_step_kernel(float* __restrict__ z, float* __restrict__ z0t_out,
         float z0[4], zn[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            float hat = EPS_HALF ? cfg_mix_h(uc[k], cc[k], lam) : cfg_mix_f(uc[k], cc[k], lam);
-            float A = tweedie_uc ? uc[k] : hat;
-            float B = renoise_uc ? uc[k] : hat;
-            float pa = __fmul_rn(A, c1);
-            float pb = __fmul_rn(B, c4);
-            if (EPS_HALF) { pa = h_round(pa); pb = h_round(pb); }
-            z0[k] = div_as_ref(__fsub_rn(zi[k], pa), c2);
-            zn[k] = __fadd_rn(__fmul_rn(c3, z0[k]), pb);
+            if (EPS_HALF) {          // the fp16-eps expression: step_math.h, shared with the masked and the panorama step
+                ddim_update_h(zi[k], uc[k], cc[k], lam, c1, c2, c3, c4, tweedie_uc, renoise_uc, z0[k], zn[k]);
+            } else {
+                const float hat = cfg_mix_f(uc[k], cc[k], lam);
+                const float A = tweedie_uc ? uc[k] : hat;
+                const float B = renoise_uc ? uc[k] : hat;
+                z0[k] = div_as_ref(__fsub_rn(zi[k], __fmul_rn(A, c1)), c2);
+                zn[k] = __fadd_rn(__fmul_rn(c3, z0[k]), __fmul_rn(B, c4));
+            }
         }
         reinterpret_cast<float4*>(z0t_out)[i] = make_float4(z0[0], z0[1], z0[2], z0[3]);
         reinterpret_cast<float4*>(z)[i] = make_float4(zn[0], zn[1], zn[2], zn[3]);
@@ -118,13 +95,8 @@ ddim_step_masked_kernel(float* __restrict__ z, float* __restrict__ z0t_out,
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const float uc = (float)ua[k], cc = (float)ub[k];
-            const float hat = cfg_mix_h(uc, cc, lam);
-            const float A = tweedie_uc ? uc : hat;
-            const float B = renoise_uc ? uc : hat;
-            const float pa = h_round(__fmul_rn(A, c1));
-            const float pb = h_round(__fmul_rn(B, c4));
-            const float z0k = div_as_ref(__fsub_rn(zi[k], pa), c2);
-            const float znk = __fadd_rn(__fmul_rn(c3, z0k), pb);
+            float z0k, znk;
+            ddim_update_h(zi[k], uc, cc, lam, c1, c2, c3, c4, tweedie_uc, renoise_uc, z0k, znk);
             const float s = (float)sv[k];
             const float proper = __fadd_rn(__fmul_rn(a, s), __fmul_rn(b, nz[k]));
             z0[k] = mk[k] ? z0k : s;

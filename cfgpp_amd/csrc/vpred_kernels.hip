@@ -12,22 +12,10 @@
 //
 // HBM-bound: per element 4 B z in + 2+2 B v in + 4 B z0t out + 4 B z out = 16 B, the eps kernel's traffic.
 #include "common.h"
+#include "step_math.h"
 #include "../../include/cfgpp_vpred.h"
 
 namespace {
-
-// the two helpers of step_kernels.hip, restated (that file keeps them private): RNE to fp16 of a value ALREADY rounded to fp32 - the
-// empty asm keeps the compiler from fusing multiply + convert into v_fma_mixlo_f16, which rounds the exact product once
-__device__ __forceinline__ float h_round(float x) {
-    asm volatile("" : "+v"(x));
-    return (float)(half_t)x;
-}
-// v_hat = v_uc + lam*(v_c - v_uc) with an fp16 rounding after each operation
-__device__ __forceinline__ float cfg_mix_h(float uc, float c, float lam) {
-    float d = h_round(__fsub_rn(c, uc));
-    float e = h_round(__fmul_rn(d, lam));
-    return h_round(__fadd_rn(uc, e));
-}
 
 struct VCoef {
     float a_z, s_v, a_v, s_z, c3, c4;

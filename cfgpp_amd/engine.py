@@ -263,6 +263,52 @@ def philox_raw(ctr4, key2, n: int, device=None) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------
+# MultiDiffusion panoramas (include/cfgpp_panorama.h)
+# ----------------------------------------------------------------------------
+def _pano_views_c(g, B: int, C_: int, name: str, z_pano: torch.Tensor, z_views: torch.Tensor):
+    """the C struct of ``g`` (``panorama.ViewGeometry``: Hp, Wp, h, w, stride, circular, n_views, chunk_views) for B chains, after
+    checking the two latent buffers against it"""
+    for n, t in (("z_pano", z_pano), ("z_views", z_views)):
+        _require_cuda(t, n)
+        if t.dtype != torch.float32:
+            raise CfgppError(f"{name}: {n} must be fp32")
+    if tuple(z_pano.shape) != (B, C_, g.Hp, g.Wp):
+        raise CfgppError(f"{name}: z_pano shape {tuple(z_pano.shape)} != [{B}, {C_}, {g.Hp}, {g.Wp}]")
+    if tuple(z_views.shape) != (g.n_views * B, C_, g.h, g.w):
+        raise CfgppError(f"{name}: z_views shape {tuple(z_views.shape)} != [{g.n_views} * {B}, {C_}, {g.h}, {g.w}]")
+    return _lib.PanoViewsC(B, C_, g.Hp, g.Wp, g.h, g.w, g.stride, int(bool(g.circular)), int(g.chunk_views))
+
+
+def gather_views(g, z_pano: torch.Tensor, z_views: torch.Tensor):
+    """``z_views`` [V * B, C, h, w] (row v * B + b) = the windows of ``z_pano`` [B, C, Hp, Wp], one launch (cfgpp_views_gather)"""
+    lib = _lib.load()
+    B, C_ = int(z_pano.shape[0]), int(z_pano.shape[1])
+    vc = _pano_views_c(g, B, C_, "gather_views", z_pano, z_views)
+    check(lib.cfgpp_views_gather(C.byref(vc), z_pano.data_ptr(), z_views.data_ptr(), _stream_ptr(z_pano)), "cfgpp_views_gather")
+
+
+def step_ddim_views(g, z_pano: torch.Tensor, z0t_pano: torch.Tensor, z_views: torch.Tensor, eps: torch.Tensor, lam: float,
+                    coeffs: Tuple[float, float, float, float], tweedie_uc: bool, renoise_uc: bool):
+    """one MultiDiffusion step in one launch (cfgpp_step_ddim_views): every view's :func:`step_ddim` from ``z_pano`` and its rows of
+    ``eps`` [V / Vc, 2 * Vc * B, C, h, w] fp16, the overlap average into ``z_pano`` (in place) / ``z0t_pano``, and the new latent
+    scattered into ``z_views``"""
+    lib = _lib.load()
+    B, C_ = int(z_pano.shape[0]), int(z_pano.shape[1])
+    vc = _pano_views_c(g, B, C_, "step_ddim_views", z_pano, z_views)
+    _require_cuda(z0t_pano, "z0t_pano")
+    _require_cuda(eps, "eps")
+    if z0t_pano.dtype != torch.float32 or z0t_pano.shape != z_pano.shape:
+        raise CfgppError("step_ddim_views: z0t_pano must be fp32 of z_pano's shape")
+    want = (g.n_views // g.chunk_views, 2 * g.chunk_views * B, C_, g.h, g.w)
+    if eps.dtype != torch.float16 or tuple(eps.shape) != want:
+        raise CfgppError(f"step_ddim_views: eps must be fp16 {list(want)}, got {eps.dtype} {list(eps.shape)}")
+    c1, c2, c3, c4 = (float(x) for x in coeffs)
+    check(lib.cfgpp_step_ddim_views(C.byref(vc), z_pano.data_ptr(), z0t_pano.data_ptr(), z_views.data_ptr(), eps.data_ptr(), float(lam),
+                                    c1, c2, c3, c4, int(bool(tweedie_uc)), int(bool(renoise_uc)), _stream_ptr(z_pano)),
+          "cfgpp_step_ddim_views")
+
+
+# ----------------------------------------------------------------------------
 # UNet engine
 # ----------------------------------------------------------------------------
 def unet_config_c(cfg: UNetConfig, H: int, W: int, max_rows: int, out_channels: Optional[int] = None) -> UNetConfigC:

@@ -210,6 +210,21 @@ class HipEngine:
             self._finite_or_raise(t)
         return eps[: self.B], eps[self.B:]
 
+    def predict_into(self, z_chunk: torch.Tensor, t: float, eps_chunk: torch.Tensor):
+        """one forward into a caller-owned slice: ``eps_chunk`` [2 * rows, 4, H, W] fp16 (uc rows, then c rows) = UNet(``z_chunk``
+        [rows, 4, H, W], t), rows = the context's B.  The panorama loop's form of ``predict``: the views' eps land where the fused
+        view step reads them, ``_eps`` is not touched."""
+        if eps_chunk.dtype != torch.float16 or tuple(eps_chunk.shape) != (2 * self.B, self.cfg.out_channels, self.H, self.W) \
+                or not eps_chunk.is_contiguous() or not eps_chunk.is_cuda:
+            raise CfgppError(f"predict_into: eps_chunk must be a contiguous fp16 GPU tensor [{2 * self.B}, {self.cfg.out_channels}, "
+                             f"{self.H}, {self.W}], got {eps_chunk.dtype} {list(eps_chunk.shape)}")
+        if int(z_chunk.shape[0]) != self.B:
+            raise CfgppError(f"predict_into: z_chunk has {int(z_chunk.shape[0])} rows, the context {self.B}")
+        self.unet.forward(z_chunk, float(t), eps_chunk)
+        self._pins.save(self.unet.rows)
+        if self.check_finite and not bool(torch.isfinite(eps_chunk).all()):
+            raise CfgppError(f"UNet output at t={t} holds non-finite values (fp16 overflow inside the UNet?) - CFGPP_CHECK_FINITE")
+
     # -- whole-loop graph replay ---------------------------------------------------------
     @property
     def graph_enabled(self) -> bool:
@@ -261,6 +276,9 @@ class HipEngine:
     # LCM (include/cfgpp_lcm.h)
     step_lcm = staticmethod(E.step_lcm)
     philox_normal = staticmethod(E.philox_normal)
+    # MultiDiffusion panoramas (include/cfgpp_panorama.h)
+    gather_views = staticmethod(E.gather_views)
+    step_ddim_views = staticmethod(E.step_ddim_views)
 
     @property
     def time_cond_proj_dim(self) -> int:
