@@ -128,6 +128,18 @@ PANORAMA_PROTOTYPES = {
     "cfgpp_step_ddim_views": (_I, [C.POINTER(PanoViewsC), _P, _P, _P, _P, _F, _F, _F, _F, _F, _I, _I, _P]),
 }
 
+# the CLIP image tower extension header (include/cfgpp_vision.h)
+VISION_PROTOTYPES = {
+    "cfgpp_vision_create": (_P, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "cfgpp_vision_destroy": (None, [_P]),
+    "cfgpp_vision_load_tensor": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_long), _I]),
+    "cfgpp_vision_finalize": (_I, [_P]),
+    "cfgpp_vision_preprocess": (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    "cfgpp_vision_encode": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "cfgpp_vision_flops": (C.c_double, [_P, _I]),
+    "cfgpp_vision_device_bytes": (C.c_double, [_P]),
+}
+
 # test hooks and development switches (cfgpp_amd/csrc/cfgpp_debug.h): same library, not part of the boundary
 DEBUG_PROTOTYPES = {
     "cfgpp_op_philox_raw": (_I, [_P, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _L, _P]),
@@ -150,6 +162,10 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cfgpp_op_perceiver_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "cfgpp_op_attention_vit": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "cfgpp_vit_attention_last_launch": (None, [C.POINTER(C.c_int)]),
+    "cfgpp_op_vit_preprocess": (_I, [_P, _I, _I, _I, _I, _P, _P]),
+    "cfgpp_op_vit_patch_rows": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_unet_ip_tokens": (_I, [_P, _P, _I]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
@@ -231,7 +247,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

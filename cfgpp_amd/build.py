@@ -34,6 +34,7 @@ SOURCES = [
     ("unet.hip", []),
     ("vae.hip", []),
     ("text.hip", []),
+    ("vision.hip", ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]),        # the CLIP image tower (include/cfgpp_vision.h): as attn_kernel.hip
 ]
 COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # `python -m cfgpp_amd.build --asan`: a SECOND library, libcfgpp_hip_asan.so, whose HOST code is AddressSanitizer-instrumented

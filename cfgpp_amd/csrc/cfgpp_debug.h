@@ -108,6 +108,23 @@ int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o,
  * head), 32-key tiles.  Refused by name, nothing launched: n_q outside 1 .. 32, S outside 1 .. 1024, a null operand. */
 int cfgpp_op_perceiver_attention(const void* q, const void* kv_x, const void* kv_l, void* o, int rows, int heads, int n_q, int S,
                                  void* stream);
+/* Self-attention of the CLIP image tower (include/cfgpp_vision.h; csrc/vision.hip), non-causal, head dims 64 / 80 / 104:
+ *   o[r][t][h*d ..] = fp16( softmax_k(q[r][t][h] . k[r][k][h] / sqrt(d)) v[r][k][h] )        t, k over the T tokens of row r
+ * Token-major fp16 operands as ONE fused QKV GEMM stores them, hidden = heads * d: qkv [rows][T][3 * hidden] with Q in columns
+ * [0, hidden), K in [hidden, 2 hidden), V in [2 hidden, 3 hidden); o [rows][T][hidden].  One wave per (row, head, block of 32
+ * queries), 32-key tiles; d = 104 zero-fills the upper half of its seventh 16-wide k-step on load (no padded buffer).  Refused by
+ * name, nothing launched: d outside {64, 80, 104}, T outside 1 .. 320, a null operand.  cfgpp_op_attention is untouched by it. */
+int cfgpp_op_attention_vit(const void* qkv, void* o, int rows, int heads, int d, int T, void* stream);
+/* test hook: what the last cfgpp_op_attention_vit call (or a tower's attention launch) issued, a host-side record zeroed at entry
+ * (a refused call reports zeros): out3 = {head dim of the instance, blocks of 32 queries per (row, head), 32-key tiles per block} */
+void cfgpp_vit_attention_last_launch(int* out3);
+/* the image front end of the tower, alone (cfgpp_vision_preprocess without an engine): img fp32 [N][3][H][W] in [0, 1] ->
+ * pixels_out fp16 [N][3][S][S] */
+int cfgpp_op_vit_preprocess(const float* img, int N, int H, int W, int S, void* pixels_out, void* stream);
+/* the im2col rows of the tower's patch convolution: pixels fp16 [N][3][S][S] -> rows fp16 [N * (S / patch)^2][Kp],
+ * rows[n * G * G + py * G + px][c * patch^2 + dy * patch + dx] = pixels[n][c][patch * py + dy][patch * px + dx], columns
+ * 3 * patch^2 .. Kp - 1 zero.  Refused: S % patch != 0, Kp < 3 * patch^2. */
+int cfgpp_op_vit_patch_rows(const void* pixels, void* rows, int N, int S, int patch, int Kp, void* stream);
 /* the [rows][n_img][cross_attention_dim] fp16 image tokens the last cfgpp_unet_image_context / cfgpp_unet_image_context_seq computed
  * (the output of the image projection, before the per-block to_k_ip / to_v_ip), copied to host_fp16_out.  rows must be the rows of
  * that call.  Error when no tokens were computed since the adapter was loaded.  Synchronises the device. */

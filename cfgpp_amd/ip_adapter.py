@@ -298,7 +298,7 @@ def assemble_hidden(pos: torch.Tensor, neg: Optional[torch.Tensor], B: int) -> t
     return torch.cat([neg.expand(B, -1, -1), pos.expand(B, -1, -1)], 0).to(torch.float16).contiguous()
 
 
-# ---- the image tower (torch ops, once per job; a HIP vision tower is out of scope) ---------------------------------------
+# ---- the image tower in torch ops (CPU devices and the fallback; on a GPU the solvers build vision.HipClipImageTower) ------
 def preprocess_image(image: torch.Tensor, size: int = 224) -> torch.Tensor:
     """[N, 3, H, W] in [0, 1] -> CLIP input [N, 3, size, size]: short side to ``size`` (torch bicubic, antialiased), centre crop,
     CLIP mean / std.  Not bit-identical to CLIPImageProcessor, which resizes with PIL."""

@@ -168,11 +168,16 @@ class StableDiffusion:
 
         # IP-Adapter ("synthetic", a safetensors path, a state dict): loaded into the UNet; used by the sample() calls that pass
         # ip_adapter_image_embeds / ip_adapter_image.  ip_adapter_dir: the folder that holds the CLIP `image_encoder/`.
+        # image_tower: "hip" (default: vision.HipClipImageTower on a GPU device) | "torch" (ip_adapter.ImageEncoder); image_encoder=
+        # overrides both.
         self._ip_job = None                 # (embeds, negative, scale, serial) of the running sample() call
         self._ip_key = None                 # what the engine's image context was last set from
         self._ip_serial = 0
         self.ip_adapter_dir = kwargs.get("ip_adapter_dir")
         self.image_encoder = kwargs.get("image_encoder")
+        self.image_tower = kwargs.get("image_tower", "hip")
+        if self.image_tower not in ("hip", "torch"):
+            raise ValueError(f"image_tower={self.image_tower!r}: 'hip' or 'torch'")
         if kwargs.get("ip_adapter") is not None:
             self.set_ip_adapter(kwargs["ip_adapter"])
 
@@ -320,12 +325,14 @@ class StableDiffusion:
         if not hasattr(self.engine, "set_image_embeds") or getattr(self.engine, "ip_adapter", None) is None:
             raise ValueError("ip_adapter_image_embeds / ip_adapter_image given, but the solver has no IP-Adapter: "
                              "get_solver(..., ip_adapter=\"synthetic\" | path | state_dict)")
-        if img is not None:                 # CLIP image tower: torch ops, once per job (ip_adapter.ImageEncoder)
+        if img is not None:                 # CLIP image tower, once per job: HIP launches (vision.HipClipImageTower) on a GPU device
             if self.image_encoder is None:
                 if not self.ip_adapter_dir:
                     raise ValueError("ip_adapter_image needs the CLIP image encoder: get_solver(..., ip_adapter_dir=<folder holding image_encoder/>)")
-                from .ip_adapter import ImageEncoder
-                self.image_encoder = ImageEncoder(self.ip_adapter_dir, self.work_device)
+                # the torch tower (ip_adapter.ImageEncoder) only on request, on a CPU device, or for a geometry the HIP tower
+                # refuses by name (vision.last_image_tower_fallbacks records it)
+                from .vision import build_image_encoder
+                self.image_encoder = build_image_encoder(self.ip_adapter_dir, self.work_device, self.image_tower)
             if getattr(self.engine.ip_adapter, "seq_input", False):
                 # a Resampler ("plus") adapter reads the tower's penultimate hidden states; its default negative is the tower on an
                 # all-zero pixel tensor (the published pipeline's zeros_like of the preprocessed image), not zero hidden states
