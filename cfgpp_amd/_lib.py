@@ -118,6 +118,12 @@ LCM_PROTOTYPES = {
     "cfgpp_unet_guidance_embedding": (_I, [_P, C.POINTER(C.c_float), _P]),
 }
 
+# the SDE extension header (include/cfgpp_sde.h): the fused DPM++ 2M / 3M SDE step and the job's first UNet input
+SDE_PROTOTYPES = {
+    "cfgpp_sde_input": (_I, [_P, _P, _F, _L, _P]),
+    "cfgpp_step_sde": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, C.POINTER(C.c_float), _I, _I, _I, _P, _S, _I, _L, _U, _P]),
+}
+
 # the MultiDiffusion panorama extension header (include/cfgpp_panorama.h): the window gather and the fused view step
 class PanoViewsC(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "C", "Hp", "Wp", "h", "w", "stride", "circular", "chunk_views")]
@@ -247,7 +253,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -1,4 +1,4 @@
-// The rounding primitives of the fused sampler steps (step_kernels.hip, vpred_kernels.hip, lcm_kernels.hip, pano_kernels.hip): ONE
+// The rounding primitives of the fused sampler steps (step_kernels.hip, vpred_kernels.hip, lcm_kernels.hip, sde_kernels.hip, pano_kernels.hip): ONE
 // definition, so that a step kernel in another file evaluates the same instruction sequence and gives the same bits.  Every file
 // that includes this is built with -ffp-contract=off (cfgpp_amd/build.py).
 #pragma once

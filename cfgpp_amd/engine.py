@@ -263,6 +263,55 @@ def philox_raw(ctr4, key2, n: int, device=None) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------
+# DPM++ 2M / 3M SDE (include/cfgpp_sde.h)
+# ----------------------------------------------------------------------------
+def sde_input(x: torch.Tensor, xc_out: torch.Tensor, s_in: float):
+    """``xc_out = h(x * s_in)``: the fp16 UNet input of step 0 of an SDE job from the fp32 latent (cfgpp_sde_input)"""
+    lib = _lib.load()
+    _require_cuda(x, "x")
+    _require_cuda(xc_out, "xc_out")
+    if x.dtype != torch.float32 or xc_out.dtype != torch.float16:
+        raise CfgppError("sde_input: x must be fp32 and xc_out fp16")
+    if x.numel() != xc_out.numel():
+        raise CfgppError("sde_input: size mismatch")
+    check(lib.cfgpp_sde_input(x.data_ptr(), xc_out.data_ptr(), float(s_in), x.numel(), _stream_ptr(x)), "cfgpp_sde_input")
+
+
+def step_sde(x: torch.Tensor, den_out: torch.Tensor, xc_out: Optional[torch.Tensor], hist1: Optional[torch.Tensor],
+             hist2: Optional[torch.Tensor], hist_out: Optional[torch.Tensor], m_uc: torch.Tensor, m_c: torch.Tensor, lam: float, coef8,
+             cfgpp: bool, n_hist: int, last: bool, seeds=None, draw: int = 0, noise: Optional[torch.Tensor] = None):
+    """one fused DPM++ 2M / 3M SDE step in place on the fp32 latent ``x`` [B, ...] (cfgpp_step_sde); ``coef8`` from ``sde.sde_coeffs``;
+    the step noise is ``noise`` (fp32, x's shape) or, with None, drawn in the kernel from ``seeds`` / ``draw``.  ``hist_out`` may be
+    ``hist2``; ``xc_out`` / ``hist_out`` may be None."""
+    lib = _lib.load()
+    f32 = (("x", x), ("den_out", den_out)) + tuple((n, t) for n, t in (("hist1", hist1), ("hist2", hist2), ("hist_out", hist_out),
+                                                                        ("noise", noise)) if t is not None)
+    f16 = (("m_uc", m_uc), ("m_c", m_c)) + ((("xc_out", xc_out),) if xc_out is not None else ())
+    for n, t in f32 + f16:
+        _require_cuda(t, n)
+        if t.numel() != x.numel():
+            raise CfgppError(f"step_sde: size mismatch ({n})")
+    if any(t.dtype != torch.float32 for _, t in f32):
+        raise CfgppError("step_sde: x, den_out, the history and noise must be fp32")
+    if any(t.dtype != torch.float16 for _, t in f16):
+        raise CfgppError("step_sde: the model output and xc_out must be fp16")
+    if len(coef8) != 8:
+        raise CfgppError("step_sde: coef8 = (sigma, a_x, a_d, a_u, a_1, a_2, a_n, s_in_next)")
+    if x.dim() < 2:
+        raise CfgppError("step_sde: x must be [B, ...]")
+    B = int(x.shape[0])
+    sd = None
+    if not last and float(coef8[6]) != 0.0 and noise is None:
+        if seeds is None:
+            raise CfgppError("step_sde: a step with a noise term needs seeds or noise")
+        sd = _seed_array(seeds, B, "step_sde")
+    arr = (C.c_float * 8)(*[float(v) for v in coef8])
+    check(lib.cfgpp_step_sde(x.data_ptr(), den_out.data_ptr(), _ptr(xc_out), _ptr(hist1), _ptr(hist2), _ptr(hist_out), m_uc.data_ptr(),
+                             m_c.data_ptr(), float(lam), arr, int(bool(cfgpp)), int(n_hist), int(bool(last)), _ptr(noise), sd, B,
+                             x.numel() // B, int(draw), _stream_ptr(x)), "cfgpp_step_sde")
+
+
+# ----------------------------------------------------------------------------
 # MultiDiffusion panoramas (include/cfgpp_panorama.h)
 # ----------------------------------------------------------------------------
 def _pano_views_c(g, B: int, C_: int, name: str, z_pano: torch.Tensor, z_views: torch.Tensor):

@@ -276,6 +276,9 @@ class HipEngine:
     # LCM (include/cfgpp_lcm.h)
     step_lcm = staticmethod(E.step_lcm)
     philox_normal = staticmethod(E.philox_normal)
+    # DPM++ 2M / 3M SDE (include/cfgpp_sde.h)
+    sde_input = staticmethod(E.sde_input)
+    step_sde = staticmethod(E.step_sde)
     # MultiDiffusion panoramas (include/cfgpp_panorama.h)
     gather_views = staticmethod(E.gather_views)
     step_ddim_views = staticmethod(E.step_ddim_views)

@@ -117,6 +117,13 @@ def get_sigmas_karras(n, sigma_min, sigma_max, rho=7.0) -> torch.Tensor:
     return append_zero(sigmas)
 
 
+def get_sigmas_exponential(n, sigma_min, sigma_max) -> torch.Tensor:
+    """k-diffusion's exponential schedule: exp(linspace(ln sigma_max, ln sigma_min, n)) with a trailing zero."""
+    import math
+    sigmas = torch.linspace(math.log(float(sigma_max)), math.log(float(sigma_min)), n).exp()
+    return append_zero(sigmas)
+
+
 def get_ancestral_step(sigma_from, sigma_to, eta=1.0):
     """latent_diffusion.py:30-37."""
     if not eta:
@@ -232,3 +239,7 @@ class SchedulerTables:
     def karras_sigmas(self) -> torch.Tensor:
         total_sigmas = (1 - self.total_alphas).sqrt() / self.total_alphas.sqrt()
         return get_sigmas_karras(self.num_sampling, total_sigmas.min(), total_sigmas.max(), rho=7.0)
+
+    def exponential_sigmas(self) -> torch.Tensor:
+        total_sigmas = (1 - self.total_alphas).sqrt() / self.total_alphas.sqrt()
+        return get_sigmas_exponential(self.num_sampling, total_sigmas.min(), total_sigmas.max())

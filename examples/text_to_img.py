@@ -64,6 +64,10 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
     ap.add_argument("--lcm_original_steps", type=int, default=None,
                     help="--method lcm: original_inference_steps of the LCM schedule (default: the checkpoint's scheduler_config.json, else 50)")
+    ap.add_argument("--eta", type=float, default=None, help="--method dpm++_2m_sde* / dpm++_3m_sde*: noise level (default 1; 0 = deterministic)")
+    ap.add_argument("--s_noise", type=float, default=None, help="--method dpm++_*_sde*: noise multiplier (default 1)")
+    ap.add_argument("--solver_type", default=None, choices=("midpoint", "heun"), help="--method dpm++_2m_sde*: second-order form (default midpoint)")
+    ap.add_argument("--sigma_schedule", default=None, choices=("karras", "exponential"), help="--method dpm++_*_sde*: sigma schedule (default karras)")
     from cfgpp_amd.freeu import add_cli_flag, cli_kwargs
     add_cli_flag(ap)
     from cfgpp_amd import vpred
@@ -107,15 +111,21 @@ def main(argv=None, solver_kwargs=None) -> None:
         from cfgpp_amd.lcm import get_lcm_solver
         if args.lcm_original_steps is not None:
             kw["lcm_original_steps"] = args.lcm_original_steps
+    from cfgpp_amd.sde import get_sde_solver, sde_solver_names
+    sde = args.method in sde_solver_names()      # the SDE samplers have their own registry too (cfgpp_amd/sde.py)
+    if sde:
+        kw.update({k: getattr(args, k) for k in ("eta", "s_noise", "solver_type", "sigma_schedule") if getattr(args, k) is not None})
     if args.model in ("sdxl", "sdxl_lightning"):
         from cfgpp_amd.latent_sdxl import get_solver
-        solver = get_lcm_solver("lcm", model="sdxl", **kw) if lcm else get_solver(args.method, **kw)
+        solver = (get_lcm_solver("lcm", model="sdxl", **kw) if lcm else get_sde_solver(args.method, model="sdxl", **kw) if sde
+                  else get_solver(args.method, **kw))
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
                                cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
                                **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
-        solver = get_lcm_solver("lcm", model="sd15", **kw) if lcm else get_solver(args.method, **kw)
+        solver = (get_lcm_solver("lcm", model="sd15", **kw) if lcm else get_sde_solver(args.method, model="sd15", **kw) if sde
+                  else get_solver(args.method, **kw))
         result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
                                **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
 
