@@ -172,6 +172,14 @@ DEBUG_PROTOTYPES = {
     "cfgpp_vit_attention_last_launch": (None, [C.POINTER(C.c_int)]),
     "cfgpp_op_vit_preprocess": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "cfgpp_op_vit_patch_rows": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "cfgpp_op_text_embed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "cfgpp_op_text_attention": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cfgpp_op_text_pool": (_I, [_P, _P, _P, _I, _I, _P]),
+    "cfgpp_op_act_inplace": (_I, [_P, _L, _I, _P]),
+    "cfgpp_op_vit_assemble": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "cfgpp_op_vit_cls_rows": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cfgpp_op_gelu_inplace": (_I, [_P, _L, _P]),
+    "cfgpp_op_broadcast_rows": (_I, [_P, _P, _L, _I, _P]),
     "cfgpp_unet_ip_tokens": (_I, [_P, _P, _I]),
     "cfgpp_op_conv_in": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_conv_in_cond": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -125,6 +125,29 @@ int cfgpp_op_vit_preprocess(const float* img, int N, int H, int W, int S, void* 
  * rows[n * G * G + py * G + px][c * patch^2 + dy * patch + dx] = pixels[n][c][patch * py + dy][patch * px + dx], columns
  * 3 * patch^2 .. Kp - 1 zero.  Refused: S % patch != 0, Kp < 3 * patch^2. */
 int cfgpp_op_vit_patch_rows(const void* pixels, void* rows, int N, int S, int patch, int Kp, void* stream);
+/* The small kernels of the CLIP text tower (csrc/text.hip), the image tower (csrc/vision.hip) and the Resampler (csrc/resampler.hip),
+ * each through the launcher its engine's plan calls (same checks, same launch geometry).  fp16 operands unless said otherwise; every
+ * row width H is read and written in 16-byte units (H % 8 == 0).  Refused by name, nothing launched: a null operand, H % 8 != 0,
+ * a count below 1, and what each entry says.
+ *   text_embed      x[b * 77 + t][:] = fp16(float(tok[id]) + float(pos[t])), id = ids[b][t] clamped to [0, vocab); ids: DEVICE int32 [B][77]
+ *   text_attention  causal self-attention over 77 tokens, head dim 64: qkv [B][77][3 H] (Q | K | V column blocks, head h at columns
+ *                   64 h of each) -> out [B][77][H]; refused: H != 64 heads
+ *   text_pool       out[b][:] = float(h[b][eos[b]][:]) with eos[b] clamped to [0, 77); h [B][77][H], eos: DEVICE int32 [B], out fp32 [B][H]
+ *   act_inplace     x = fp16(act(x)) over n values (csrc/small_kernels.hip; the MLP activation of both towers): act 0 quick_gelu
+ *                   x sigmoid(1.702 x), 1 gelu x / 2 (1 + erff(x / sqrt 2)); refused: n % 8 != 0, act outside {0, 1}
+ *   vit_assemble    x[n][0] = cls + pos[0], x[n][1 + p] = patch[n][p] + pos[1 + p] (fp32 sum, rounded once); patch [N][T - 1][H],
+ *                   cls [H], pos [T][H], x [N][T][H]; refused: T < 2
+ *   vit_cls_rows    dst[n][:] = x[n][0][:]; x [N][T][H], dst [N][H]
+ *   gelu_inplace    x = fp16(gelu(x)) over n values by common.h's gelu_erf_f (the Resampler's feed-forward; NOT act_inplace's erff)
+ *   broadcast_rows  dst[r][:] = fp16(src[:]) for r < rows; src fp32 [n], dst [rows][n]; refused: n % 8 != 0 */
+int cfgpp_op_text_embed(const int* ids, const void* tok, const void* pos, void* x, int B, int H, int vocab, void* stream);
+int cfgpp_op_text_attention(const void* qkv, void* out, int B, int heads, int H, void* stream);
+int cfgpp_op_text_pool(const void* h, const int* eos, float* out, int B, int H, void* stream);
+int cfgpp_op_act_inplace(void* x, long n, int act, void* stream);
+int cfgpp_op_vit_assemble(const void* patch, const void* cls, const void* pos, void* x, int N, int T, int H, void* stream);
+int cfgpp_op_vit_cls_rows(const void* x, void* dst, int N, int T, int H, void* stream);
+int cfgpp_op_gelu_inplace(void* x, long n, void* stream);
+int cfgpp_op_broadcast_rows(const float* src, void* dst, long n, int rows, void* stream);
 /* the [rows][n_img][cross_attention_dim] fp16 image tokens the last cfgpp_unet_image_context / cfgpp_unet_image_context_seq computed
  * (the output of the image projection, before the per-block to_k_ip / to_v_ip), copied to host_fp16_out.  rows must be the rows of
  * that call.  Error when no tokens were computed since the adapter was loaded.  Synchronises the device. */

@@ -19,6 +19,9 @@
 #include "cfgpp_debug.h"
 #include "igemm.h"
 
+// the towers' MLP activation (small_kernels.hip; used by text.hip and vision.hip), in place: act 0 quick_gelu, 1 erf gelu; n % 8 == 0
+int act_inplace_launch(half_t* x, long n, int act, hipStream_t s);
+
 namespace {
 
 

@@ -201,6 +201,14 @@ int broadcast_rows_launch(const float* src, half_t* dst, long n, int rows, hipSt
     return 0;
 }
 
+// the Resampler's GELU and latent broadcast on their own.  gelu_erf_f (common.h) is the Abramowitz-Stegun erfc with hardware rcp / exp2,
+// not the erff of act_inplace (small_kernels.hip, the towers' act 1): another function in the last bits, so it keeps its kernel.
+extern "C" int cfgpp_op_gelu_inplace(void* x, long n, void* stream) { return gelu_inplace_launch((half_t*)x, n, (hipStream_t)stream); }
+
+extern "C" int cfgpp_op_broadcast_rows(const float* src, void* dst, long n, int rows, void* stream) {
+    return broadcast_rows_launch(src, (half_t*)dst, n, rows, (hipStream_t)stream);
+}
+
 extern "C" int cfgpp_op_perceiver_attention(const void* q, const void* kv_x, const void* kv_l, void* o, int rows, int heads, int n_q,
                                             int S, void* stream) {
     return perceiver_attn_launch((const half_t*)q, (const half_t*)kv_x, (const half_t*)kv_l, (half_t*)o, rows, heads, n_q, S,

@@ -348,6 +348,33 @@ int fanout_rows_launch(half_t* const* p, const long* row_elems, int nseg, int h,
 }
 
 
+// The MLP activation of the CLIP text and image towers (text.hip, vision.hip), in place, 8 values per thread: act 0 = quick_gelu
+// x * sigmoid(1.702 x) (CLIP-L, ViT-L/14), 1 = gelu by erff (OpenCLIP-bigG, ViT-H/14, ViT-bigG/14).  n % 8 == 0.
+__global__ void __launch_bounds__(256)
+act_inplace_kernel(half_t* __restrict__ x, long n8, int act) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    half8_t v = *reinterpret_cast<half8_t*>(x + i * 8);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float f = (float)v[k];
+        const float r = act == 0 ? f / (1.0f + __expf(-1.702f * f)) : 0.5f * f * (1.0f + erff(f * 0.70710678118654752f));
+        v[k] = (half_t)r;
+    }
+    *reinterpret_cast<half8_t*>(x + i * 8) = v;
+}
+
+int act_inplace_launch(half_t* x, long n, int act, hipStream_t s) {
+    CFGPP_REQUIRE(x, "act_inplace: null operand");
+    CFGPP_REQUIRE(n > 0 && n % 8 == 0 && n / 8 < (1L << 39), "act_inplace: n=%ld (a positive multiple of 8)", n);
+    CFGPP_REQUIRE(act == 0 || act == 1, "act_inplace: activation %d (0 quick_gelu | 1 gelu)", act);
+    hipLaunchKernelGGL(act_inplace_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, x, n / 8, act);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int cfgpp_op_act_inplace(void* x, long n, int act, void* stream) { return act_inplace_launch((half_t*)x, n, act, (hipStream_t)stream); }
+
 // ---------------------------------------------------------------------------
 // AutoencoderKL posterior (diffusers DiagonalGaussianDistribution, reached from
 // latent_diffusion.py:117-121 / latent_sdxl.py:150-153):  moments = quant_conv(conv_out) (1x1, 8->8),

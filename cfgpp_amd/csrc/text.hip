@@ -3,7 +3,8 @@
 // projected pooled output of the second tower).  Runs once per prompt, off the per-step path - it exists so that a job needs
 // no torch ops at all, not for speed.  Same building blocks as the UNet: igemm linear layers (bias / residual epilogues),
 // cfgpp_op_layernorm, skinny_gemm for the pooled projection; new here: token + position embedding gather, causal
-// self-attention over the 77 tokens (head dim 64 in both CLIP-L and OpenCLIP-bigG), quick_gelu / gelu.
+// self-attention over the 77 tokens (head dim 64 in both CLIP-L and OpenCLIP-bigG); quick_gelu / gelu is act_inplace of
+// small_kernels.hip, shared with the image tower.
 //
 // hidden_states[k], k = 0 .. L: the residual stream before layer k (k = L: after the last layer);
 // last_hidden_state = final_layer_norm(hidden_states[L]); pooled = last_hidden_state[eos position] @ text_projection^T.
@@ -92,21 +93,6 @@ text_attn_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int H
     }
 }
 
-// in place: act 0 = quick_gelu x * sigmoid(1.702 x) (CLIP-L), 1 = gelu (erf; OpenCLIP-bigG)
-__global__ void __launch_bounds__(256)
-text_act_kernel(half_t* __restrict__ x, long n8, int act) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    half8_t v = *reinterpret_cast<half8_t*>(x + i * 8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float f = (float)v[k];
-        const float r = act == 0 ? f / (1.0f + __expf(-1.702f * f)) : 0.5f * f * (1.0f + erff(f * 0.70710678118654752f));
-        v[k] = (half_t)r;
-    }
-    *reinterpret_cast<half8_t*>(x + i * 8) = v;
-}
-
 // pooled input: row (b, eos[b]) of the final-LayerNorm output, as fp32
 __global__ void __launch_bounds__(128)
 text_pool_kernel(const half_t* __restrict__ h, const int* __restrict__ eos, float* __restrict__ out, int H) {
@@ -115,6 +101,32 @@ text_pool_kernel(const half_t* __restrict__ h, const int* __restrict__ eos, floa
     e = e < 0 ? 0 : (e >= T ? T - 1 : e);
     const half_t* src = h + ((long)b * T + e) * H;
     for (int c = threadIdx.x; c < H; c += 128) out[(long)b * H + c] = (float)src[c];
+}
+
+// the launchers of the four kernels above: what the plan's closures run, and what the hooks of cfgpp_debug.h run
+int text_embed_launch(const int* ids, const half_t* tok, const half_t* pos, half_t* x, int B, int H, int vocab, hipStream_t s) {
+    CFGPP_REQUIRE(ids && tok && pos && x, "text_embed: null operand");
+    CFGPP_REQUIRE(B >= 1 && H >= 8 && H % 8 == 0 && vocab >= 1, "text_embed: B=%d H=%d vocab=%d (H a positive multiple of 8)", B, H, vocab);
+    hipLaunchKernelGGL(text_embed_kernel, dim3(B * T), dim3(128), 0, s, ids, tok, pos, x, H, vocab);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int text_attn_launch(const half_t* qkv, half_t* out, int B, int heads, int H, hipStream_t s) {
+    CFGPP_REQUIRE(qkv && out, "text_attention: null operand");
+    CFGPP_REQUIRE(B >= 1 && heads >= 1, "text_attention: B=%d heads=%d", B, heads);
+    CFGPP_REQUIRE(H % 8 == 0 && H == heads * 64, "text_attention: H=%d must be heads=%d x 64", H, heads);
+    hipLaunchKernelGGL(text_attn_kernel, dim3(heads, B), dim3(128), 0, s, qkv, out, H, 0.125f);        // 64^-1/2
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
+int text_pool_launch(const half_t* h, const int* eos, float* out, int B, int H, hipStream_t s) {
+    CFGPP_REQUIRE(h && eos && out, "text_pool: null operand");
+    CFGPP_REQUIRE(B >= 1 && H >= 1, "text_pool: B=%d H=%d", B, H);
+    hipLaunchKernelGGL(text_pool_kernel, dim3(B), dim3(128), 0, s, h, eos, out, H);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 void text_param_table(cfgpp_text* t) {
@@ -135,6 +147,18 @@ void text_param_table(cfgpp_text* t) {
 }  // namespace
 
 extern "C" {
+
+int cfgpp_op_text_embed(const int* ids, const void* tok, const void* pos, void* x, int B, int H, int vocab, void* stream) {
+    return text_embed_launch(ids, (const half_t*)tok, (const half_t*)pos, (half_t*)x, B, H, vocab, (hipStream_t)stream);
+}
+
+int cfgpp_op_text_attention(const void* qkv, void* out, int B, int heads, int H, void* stream) {
+    return text_attn_launch((const half_t*)qkv, (half_t*)out, B, heads, H, (hipStream_t)stream);
+}
+
+int cfgpp_op_text_pool(const void* h, const int* eos, float* out, int B, int H, void* stream) {
+    return text_pool_launch((const half_t*)h, eos, out, B, H, (hipStream_t)stream);
+}
 
 cfgpp_text* cfgpp_text_create(int vocab, int hidden, int layers, int heads, int intermediate, int act, int proj_dim,
                               int max_batch, int device_id) {
@@ -202,7 +226,6 @@ int cfgpp_text_finalize(cfgpp_text* t) {
     t->d_eos = (int*)t->dmalloc((size_t)R * sizeof(int));
     CFGPP_REQUIRE(t->x && t->h && t->qkv && t->att && t->ff && t->pool_in && t->d_ids && t->d_eos, "text_finalize: hipMalloc failed");
     cfgpp_text* tt = t;
-    const float scale = 0.125f;                       // 64^-1/2
     // hidden_states[k] snapshot: the residual stream as it stands when layer k is about to run (k = L: after the last one)
     auto snapshot = [&](int k) {
         t->plan.push_back([tt, k, H](hipStream_t s, int r) {
@@ -211,11 +234,7 @@ int cfgpp_text_finalize(cfgpp_text* t) {
             return 0;
         });
     };
-    t->plan.push_back([tt, H](hipStream_t s, int r) {
-        hipLaunchKernelGGL(text_embed_kernel, dim3(r * T), dim3(128), 0, s, tt->d_ids, tt->tok_emb, tt->pos_emb, tt->x, H, tt->vocab);
-        CFGPP_HIP_CHECK(hipGetLastError());
-        return 0;
-    });
+    t->plan.push_back([tt, H](hipStream_t s, int r) { return text_embed_launch(tt->d_ids, tt->tok_emb, tt->pos_emb, tt->x, r, H, tt->vocab, s); });
     for (int l = 0; l < t->layers && B.ok; ++l) {
         const std::string p = "text_model.encoder.layers." + std::to_string(l);
         snapshot(l);
@@ -234,20 +253,11 @@ int cfgpp_text_finalize(cfgpp_text* t) {
         if (!B.ok) break;
         P.layernorm(t->x, t->h, g1, b1, T, H);
         P.linear(t->h, H, t->qkv, 3 * H, wqkv, bqkv, nullptr, T);
-        t->plan.push_back([tt, H, scale](hipStream_t s, int r) {
-            hipLaunchKernelGGL(text_attn_kernel, dim3(tt->heads, r), dim3(128), 0, s, tt->qkv, tt->att, H, scale);
-            CFGPP_HIP_CHECK(hipGetLastError());
-            return 0;
-        });
+        t->plan.push_back([tt, H](hipStream_t s, int r) { return text_attn_launch(tt->qkv, tt->att, r, tt->heads, H, s); });
         P.linear(t->att, H, t->x, H, wo, bo, t->x, T);                  // x += out_proj(att)   (residual in place)
         P.layernorm(t->x, t->h, g2, b2, T, H);
         P.linear(t->h, H, t->ff, I, w1, bf1, nullptr, T);
-        t->plan.push_back([tt, I](hipStream_t s, int r) {
-            const long n8 = (long)r * T * I / 8;
-            hipLaunchKernelGGL(text_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, tt->ff, n8, tt->act);
-            CFGPP_HIP_CHECK(hipGetLastError());
-            return 0;
-        });
+        t->plan.push_back([tt, I](hipStream_t s, int r) { return act_inplace_launch(tt->ff, (long)r * T * I, tt->act, s); });
         P.linear(t->ff, I, t->x, H, w2, bf2, t->x, T);                   // x += fc2(act(fc1(ln2(x))))
     }
     CFGPP_REQUIRE(B.ok, "text_finalize: %s", B.err.c_str());
@@ -264,8 +274,7 @@ int cfgpp_text_finalize(cfgpp_text* t) {
             t->wproj = B.linear("text_projection.weight");
             t->plan.push_back([tt, H](hipStream_t s, int r) {
                 if (!tt->out_pooled) return 0;
-                hipLaunchKernelGGL(text_pool_kernel, dim3(r), dim3(128), 0, s, tt->h, tt->d_eos, tt->pool_in, H);
-                CFGPP_HIP_CHECK(hipGetLastError());
+                if (int e = text_pool_launch(tt->h, tt->d_eos, tt->pool_in, r, H, s)) return e;
                 return cfgpp_op_skinny_gemm(tt->pool_in, H, tt->wproj, nullptr, nullptr, 0, tt->out_pooled, tt->proj, r, tt->proj, H, 0, 0, s);
             });
         }

@@ -314,19 +314,13 @@ vit_assemble_kernel(const half_t* __restrict__ patch, const half_t* __restrict__
     }
 }
 
-// in place: act 0 = quick_gelu x * sigmoid(1.702 x) (ViT-L/14), 1 = gelu (erf; ViT-H/14, ViT-bigG/14).  text.hip's text_act_kernel restated.
-__global__ void __launch_bounds__(256)
-vit_act_kernel(half_t* __restrict__ x, long n8, int act) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n8) return;
-    half8_t v = *reinterpret_cast<half8_t*>(x + i * 8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float f = (float)v[k];
-        const float r = act == 0 ? f / (1.0f + __expf(-1.702f * f)) : 0.5f * f * (1.0f + erff(f * 0.70710678118654752f));
-        v[k] = (half_t)r;
-    }
-    *reinterpret_cast<half8_t*>(x + i * 8) = v;
+int vit_assemble_launch(const half_t* patch, const half_t* cls, const half_t* pos, half_t* x, int N, int T, int H, hipStream_t s) {
+    CFGPP_REQUIRE(patch && cls && pos && x, "vit_assemble: null operand");
+    CFGPP_REQUIRE(N >= 1 && T >= 2 && (long)N * T < (1L << 31) && H >= 8 && H % 8 == 0,
+                  "vit_assemble: N=%d T=%d H=%d (a class token and at least one patch; H a positive multiple of 8)", N, T, H);
+    hipLaunchKernelGGL(vit_assemble_kernel, dim3(N * T), dim3(128), 0, s, patch, cls, pos, x, H, T);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 // the class-token rows: dst[n][:] = x[n][0][:]
@@ -335,6 +329,14 @@ vit_cls_rows_kernel(const half_t* __restrict__ x, half_t* __restrict__ dst, int 
     const int n = blockIdx.x;
     for (int c = threadIdx.x * 8; c < H; c += 128 * 8)
         *reinterpret_cast<half8_t*>(dst + (long)n * H + c) = *reinterpret_cast<const half8_t*>(x + (long)n * T * H + c);
+}
+
+int vit_cls_rows_launch(const half_t* x, half_t* dst, int N, int T, int H, hipStream_t s) {
+    CFGPP_REQUIRE(x && dst, "vit_cls_rows: null operand");
+    CFGPP_REQUIRE(N >= 1 && T >= 1 && H >= 8 && H % 8 == 0, "vit_cls_rows: N=%d T=%d H=%d (H a positive multiple of 8)", N, T, H);
+    hipLaunchKernelGGL(vit_cls_rows_kernel, dim3(N), dim3(128), 0, s, x, dst, H, T);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    return 0;
 }
 
 const char* VM = "vision_model.";
@@ -373,6 +375,14 @@ int cfgpp_op_vit_preprocess(const float* img, int N, int H, int W, int S, void* 
 
 int cfgpp_op_vit_patch_rows(const void* pixels, void* rows, int N, int S, int patch, int Kp, void* stream) {
     return vit_patch_rows_launch((const half_t*)pixels, (half_t*)rows, N, S, patch, Kp, (hipStream_t)stream);
+}
+
+int cfgpp_op_vit_assemble(const void* patch, const void* cls, const void* pos, void* x, int N, int T, int H, void* stream) {
+    return vit_assemble_launch((const half_t*)patch, (const half_t*)cls, (const half_t*)pos, (half_t*)x, N, T, H, (hipStream_t)stream);
+}
+
+int cfgpp_op_vit_cls_rows(const void* x, void* dst, int N, int T, int H, void* stream) {
+    return vit_cls_rows_launch((const half_t*)x, (half_t*)dst, N, T, H, (hipStream_t)stream);
 }
 
 cfgpp_vision* cfgpp_vision_create(int hidden, int layers, int heads, int intermediate, int act, int proj_dim, int image_size,
@@ -490,11 +500,7 @@ int cfgpp_vision_finalize(cfgpp_vision* t) {
     };
     t->plan.push_back([tt](hipStream_t s, int r) { return vit_patch_rows_launch(tt->in_pixels, tt->rows, r, tt->S, tt->ps, tt->Kp, s); });
     P.linear(t->rows, Kp, t->patch, H, t->wpatch, nullptr, nullptr, PP);
-    t->plan.push_back([tt, H, T](hipStream_t s, int r) {
-        hipLaunchKernelGGL(vit_assemble_kernel, dim3(r * T), dim3(128), 0, s, tt->patch, tt->cls, tt->pos, tt->h, H, T);
-        CFGPP_HIP_CHECK(hipGetLastError());
-        return 0;
-    });
+    t->plan.push_back([tt, H, T](hipStream_t s, int r) { return vit_assemble_launch(tt->patch, tt->cls, tt->pos, tt->h, r, T, H, s); });
     {
         const float* g = B.f32(vm + "pre_layrnorm.weight"); const float* b = B.f32(vm + "pre_layrnorm.bias");
         P.layernorm(t->h, t->x, g, b, T, H);
@@ -523,12 +529,7 @@ int cfgpp_vision_finalize(cfgpp_vision* t) {
         P.linear(t->att, H, t->x, H, wo, bo, t->x, T);                  // x += out_proj(att)   (residual in place)
         P.layernorm(t->x, t->h, g2, b2, T, H);
         P.linear(t->h, H, t->ff, I, w1, bf1, nullptr, T);
-        t->plan.push_back([tt, I, T](hipStream_t s, int r) {
-            const long n8 = (long)r * T * I / 8;
-            hipLaunchKernelGGL(vit_act_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, tt->ff, n8, tt->act);
-            CFGPP_HIP_CHECK(hipGetLastError());
-            return 0;
-        });
+        t->plan.push_back([tt, I, T](hipStream_t s, int r) { return act_inplace_launch(tt->ff, (long)r * T * I, tt->act, s); });
         P.linear(t->ff, I, t->x, H, w2, bf2, t->x, T);                   // x += fc2(act(fc1(ln2(x))))
     }
     CFGPP_REQUIRE(B.ok, "vision_finalize: %s", B.err.c_str());
@@ -540,9 +541,9 @@ int cfgpp_vision_finalize(cfgpp_vision* t) {
         t->macs_per_row += (double)H * t->proj;
         t->plan.push_back([tt, gf, bf, H, T](hipStream_t s, int r) {
             if (!tt->out_embeds) return 0;
-            hipLaunchKernelGGL(vit_cls_rows_kernel, dim3(r), dim3(128), 0, s, tt->x, tt->cls_x, H, T);
-            CFGPP_HIP_CHECK(hipGetLastError());
-            int e = cfgpp_op_layernorm(tt->cls_x, tt->cls_h, gf, bf, r, H, 1e-5f, s);
+            int e = vit_cls_rows_launch(tt->x, tt->cls_x, r, T, H, s);
+            if (e) return e;
+            e = cfgpp_op_layernorm(tt->cls_x, tt->cls_h, gf, bf, r, H, 1e-5f, s);
             if (e) return e;
             e = cfgpp_op_f16_to_f32_rows(tt->cls_h, tt->pool_in, r, H, H, 0, s);
             if (e) return e;

@@ -377,3 +377,57 @@ def vae_posterior(conv_out, qw, qb, noise, scale, moments=True, out=None, out_mo
     m = _dst(out_moments, (B, 8, HW), torch.float32) if moments else None
     check(lib().cfgpp_op_vae_posterior(P(conv_out), P(qw), P(qb), P(noise), P(z), P(m), B, HW, float(scale), stream()), "cfgpp_op_vae_posterior")
     return z, m
+
+
+# ---- the towers' small kernels (csrc/text.hip, csrc/vision.hip, csrc/resampler.hip, act_inplace of csrc/small_kernels.hip) and the
+# ControlNet kernels, every argument of the C entry points; destinations are the caller's (guarded) tensors -----------------------------
+def text_embed(ids, tok, pos, x, B, H, vocab):
+    """ids: device int32 [B, 77]; tok [vocab, H], pos [77, H], x [B * 77, H] fp16"""
+    check(lib().cfgpp_op_text_embed(P(ids), P(tok), P(pos), P(x), B, H, vocab, stream()), "cfgpp_op_text_embed")
+    return x
+
+
+def text_attention(qkv, out, B, heads, H):
+    check(lib().cfgpp_op_text_attention(P(qkv), P(out), B, heads, H, stream()), "cfgpp_op_text_attention")
+    return out
+
+
+def text_pool(h, eos, out, B, H):
+    """h [B, 77, H] fp16, eos: device int32 [B], out [B, H] fp32"""
+    check(lib().cfgpp_op_text_pool(P(h), P(eos), P(out), B, H, stream()), "cfgpp_op_text_pool")
+    return out
+
+
+def act_inplace(x, n, act):
+    check(lib().cfgpp_op_act_inplace(P(x), n, act, stream()), "cfgpp_op_act_inplace")
+    return x
+
+
+def gelu_inplace(x, n):
+    check(lib().cfgpp_op_gelu_inplace(P(x), n, stream()), "cfgpp_op_gelu_inplace")
+    return x
+
+
+def vit_assemble(patch, cls, pos, x, N, T, H):
+    check(lib().cfgpp_op_vit_assemble(P(patch), P(cls), P(pos), P(x), N, T, H, stream()), "cfgpp_op_vit_assemble")
+    return x
+
+
+def vit_cls_rows(x, dst, N, T, H):
+    check(lib().cfgpp_op_vit_cls_rows(P(x), P(dst), N, T, H, stream()), "cfgpp_op_vit_cls_rows")
+    return dst
+
+
+def broadcast_rows(src, dst, n, rows):
+    check(lib().cfgpp_op_broadcast_rows(P(src), P(dst), n, rows, stream()), "cfgpp_op_broadcast_rows")
+    return dst
+
+
+def cn_conv3x3(x, in_kind, out, out_pad, wk, bias, R, Ci, Co, Hi, Wi, stride, silu):
+    check(lib().cfgpp_op_cn_conv3x3(P(x), in_kind, P(out), out_pad, P(wk), P(bias), R, Ci, Co, Hi, Wi, stride, silu, stream()), "cfgpp_op_cn_conv3x3")
+    return out
+
+
+def residual_nchw(src, out, rows, H, W, C, scale):
+    check(lib().cfgpp_op_residual_nchw(P(src), P(out), rows, H, W, C, float(scale), stream()), "cfgpp_op_residual_nchw")
+    return out

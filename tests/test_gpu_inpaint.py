@@ -26,7 +26,11 @@ def rel_l2(a, b):
 
 
 # ---------------------------------------------------------------------------------------------------- masked step kernel
-@pytest.mark.parametrize("shape", [(8, 4, 64, 64), (3, 4, 24, 40)])
+# (3, 4, 2, 2): hw = 4, one float4 per (row, channel) and 12 working threads in all; (2, 4, 4, 6): hw = 24, a partial block; (2, 4, 512, 514):
+# B * hw = 526336 float4 items for the 2048 x 256 = 524288 threads of the capped grid, a second trip of the grid-stride loop.  The mask
+# is drawn per batch row (no two rows share one), and every operand lives between guard elements (tests/test_gpu_small.py) that must
+# keep their bits.
+@pytest.mark.parametrize("shape", [(8, 4, 64, 64), (3, 4, 24, 40), (3, 4, 2, 2), (2, 4, 4, 6), (2, 4, 512, 514)])
 @pytest.mark.parametrize("cfgpp,last", [(True, False), (False, False), (True, True)])
 def test_masked_step_matches_torch_where_on_the_device(shape, cfgpp, last):
     need_gpu()
@@ -40,13 +44,30 @@ def test_masked_step_matches_torch_where_on_the_device(shape, cfgpp, last):
     a, b = (1.0, 0.0) if last else (sq[2], sq[3])
     g = torch.Generator().manual_seed(sum(shape))
     B, _, h, w = shape
+    from test_gpu_small import guarded, guards_intact
+
+    def gin(t):
+        buf, v = guarded(tuple(t.shape), t.dtype)
+        v.copy_(t.cuda())
+        return buf, v
     z = torch.randn(shape, generator=g).cuda()
-    euc, ec = torch.randn(shape, generator=g).half().cuda(), torch.randn(shape, generator=g).half().cuda()
-    src = (torch.randn(shape, generator=g) * 0.8).half().cuda()
-    noise = torch.randn(shape, generator=g).cuda()
+    (bu, euc), (bc, ec) = gin(torch.randn(shape, generator=g).half()), gin(torch.randn(shape, generator=g).half())
+    bs, src = gin((torch.randn(shape, generator=g) * 0.8).half())
+    bn, noise = gin(torch.randn(shape, generator=g))
     m = (torch.rand(B, 1, h, w, generator=g) < 0.4).cuda()
-    zk, z0k = z.clone(), torch.empty_like(z)
-    E.step_ddim_masked(zk, z0k, euc, ec, 0.6, co, False, cfgpp, m.to(torch.uint8), src, noise, a, b)
+    for r in range(1, B):                                   # a mask of its own in every batch row: redraw a row that repeats an earlier one
+        while any(torch.equal(m[r], m[q]) for q in range(r)):
+            m[r] = (torch.rand(1, h, w, generator=g) < 0.4).cuda()
+    assert all(not torch.equal(m[r], m[q]) for r in range(B) for q in range(r))
+    mbuf = torch.full((2 * 4096 + m.numel(),), 0xA5, dtype=torch.uint8, device="cuda")       # the mask bytes between guard bytes of their own
+    m8 = mbuf[4096:-4096].view(B, 1, h, w)
+    m8.copy_(m)
+    (bz, zk), (b0, z0k) = guarded(shape, torch.float32), guarded(shape, torch.float32)
+    zk.copy_(z)
+    E.step_ddim_masked(zk, z0k, euc, ec, 0.6, co, False, cfgpp, m8, src, noise, a, b)
+    torch.cuda.synchronize()
+    assert all(guards_intact(x) for x in (bz, b0, bu, bc, bs, bn)) and bool((mbuf[:4096] == 0xA5).all()) and bool((mbuf[-4096:] == 0xA5).all())
+    assert torch.equal(m8.bool(), m)
     zp, z0p = z.clone(), torch.empty_like(z)
     E.step_ddim(zp, z0p, euc, ec, 0.6, co, False, cfgpp)
     want_z = torch.where(m.bool(), zp, a * src.float() + b * noise)

@@ -143,3 +143,118 @@ def test_ancestral_solvers_run_on_gpu():
             outs.append((den.float().cpu(), x.float().cpu()))
         assert outs[0][0].shape == (2, 4, 16, 16) and torch.isfinite(outs[0][1]).all()
         assert torch.equal(outs[0][1], outs[1][1]), name
+
+
+# ---------------------------------------------------------------------------------------------------- launch edges, guarded buffers
+# The tests above run sizes such as [8, 4, 64, 64]: whole blocks, a grid below the cap of 2048 blocks x 256 threads, so every thread
+# runs its grid-stride loop body once.  Here: one thread, a partial last block on both sides of a block boundary, and one item more
+# than the capped grid has threads (thread 0 takes a second trip) - float4 kernels in units of 4 values.  Every operand lives in an
+# allocation with guard elements before and after (tests/test_gpu_small.py: a NaN bit pattern, which also fills every destination
+# before the launch), and the guards must hold their bits afterwards.  Same bit-exact CPU emulations as above.
+F4_SIZES = (4, 1020, 1024, 1028, 4 * 2048 * 256 + 4)
+SC_SIZES = (1, 255, 257, 2048 * 256 + 1)
+
+
+def _gin(t):
+    """a CPU tensor -> (guarded allocation, its device view holding t)"""
+    from test_gpu_small import guarded
+    buf, v = guarded(tuple(t.shape), t.dtype)
+    v.copy_(t.cuda())
+    return buf, v
+
+
+def _gout(n, dtype):
+    from test_gpu_small import guarded
+    return guarded((n,), dtype)
+
+
+def _intact(*bufs):
+    from test_gpu_small import guards_intact
+    return all(guards_intact(b) for b in bufs)
+
+
+def _same(dev_view, want):
+    it = torch.int16 if want.dtype == torch.float16 else torch.int32
+    return torch.equal(dev_view.cpu().view(it), want.contiguous().view(it))
+
+
+@pytest.mark.parametrize("n", F4_SIZES)
+@pytest.mark.parametrize("latent,eps", [("f32", "f16"), ("f32", "f32"), ("f16", "f16")])
+def test_ddim_step_edges(E, n, latent, eps):
+    """ddim_step_kernel<true>, <false> and ddim_step_h_kernel: all four (tweedie, renoise) pairs at the small sizes, CFG++ at the
+    size that wraps the grid"""
+    from cfgpp_amd.coeffs import ddim_coeffs_pinned
+    from cfgpp_amd.schedule import SchedulerTables
+    from mock_engine import emulate_step_ddim
+    tb = SchedulerTables(50)
+    co = ddim_coeffs_pinned(tb.ddim_sqrt_coeffs(tb.timesteps[7]), eps_half=eps == "f16")
+    zt, et = (torch.float32 if k == "f32" else torch.float16 for k in (latent, eps))
+    g = torch.Generator().manual_seed(n % 9973 + len(latent + eps))
+    z = torch.randn(n, generator=g).to(zt)
+    eu, ec = torch.randn(n, generator=g).to(et), torch.randn(n, generator=g).to(et)
+    flags = [(False, True)] if n > 4096 else [(False, False), (False, True), (True, False), (True, True)]
+    for tw, rn in flags:
+        zr, z0r = z.clone(), torch.empty_like(z)
+        emulate_step_ddim(zr, z0r, eu, ec, 0.6, co, tw, rn)
+        (bz, zd), (b0, z0d), (bu, ud), (bc, cd) = _gin(z), _gout(n, zt), _gin(eu), _gin(ec)
+        E.step_ddim(zd, z0d, ud, cd, 0.6, co, tw, rn)
+        torch.cuda.synchronize()
+        assert _intact(bz, b0, bu, bc), (n, tw, rn, "guard elements written")
+        assert _same(z0d, z0r) and _same(zd, zr), (n, latent, eps, tw, rn)
+        assert _same(ud, eu) and _same(cd, ec)
+
+
+@pytest.mark.parametrize("n", SC_SIZES)
+def test_kdiff_kernels_edges(E, n):
+    """kdiff_input (both modes), kdiff_step at the variant / form / solver combinations of test_kdiff_kernel_vs_emulation_large on the
+    Euler and the 2M branch, kdiff_denoise"""
+    from cfgpp_amd.coeffs import kdiff_coeffs
+    from cfgpp_amd.schedule import SchedulerTables
+    from mock_engine import emulate_kdiff_denoise, emulate_kdiff_input, emulate_step_kdiff
+    sig = SchedulerTables(20).karras_sigmas()
+    g = torch.Generator().manual_seed(n % 9973)
+    x = (torch.randn(n, generator=g) * 3).half()
+    old = torch.randn(n, generator=g).half()
+    eu, ec = torch.randn(n, generator=g).half(), torch.randn(n, generator=g).half()
+    for mode, s in ((0, 1.7321), (1, 0.5774), (0, -0.5774)):
+        xr = torch.empty_like(x)
+        emulate_kdiff_input(x, xr, s, mode)
+        (bx, xd), (bo, od) = _gin(x), _gout(n, torch.float16)
+        E.kdiff_input(xd, od, s, mode)
+        torch.cuda.synchronize()
+        assert _intact(bx, bo) and _same(od, xr) and _same(xd, x), (n, mode, s)
+    for variant, xl_form, solver in [(0, False, "dpm2m"), (1, False, "dpm2m"), (2, True, "dpm2m"), (1, False, "euler"), (0, False, "euler")]:
+        for i in (0, 5):
+            first = solver == "euler" or i == 0
+            coef, euler = kdiff_coeffs(0.6, sig, i, first, xl_form)
+            xr, dr, orr = x.clone(), torch.empty_like(x), old.clone()
+            emulate_step_kdiff(xr, dr, orr, eu, ec, coef, variant, xl_form, euler, solver != "euler")
+            (bx, xd), (bd, dd), (bo, od), (bu, ud), (bc, cd) = _gin(x), _gout(n, torch.float16), _gin(old), _gin(eu), _gin(ec)
+            E.step_kdiff(xd, dd, od, ud, cd, coef, variant, xl_form, euler, solver != "euler")
+            torch.cuda.synchronize()
+            assert _intact(bx, bd, bo, bu, bc), (n, variant, xl_form, solver, i, "guard elements written")
+            assert _same(xd, xr) and _same(dd, dr) and _same(od, orr), (n, variant, xl_form, solver, i)
+    dr, ur = torch.empty_like(x), torch.empty_like(x)
+    emulate_kdiff_denoise(x, eu, ec, 0.6, 3.217, dr, ur)
+    (bx, xd), (bu, ud), (bc, cd), (bd, dd), (bn, nd) = _gin(x), _gin(eu), _gin(ec), _gout(n, torch.float16), _gout(n, torch.float16)
+    E.kdiff_denoise(xd, ud, cd, 0.6, 3.217, dd, nd)
+    torch.cuda.synchronize()
+    assert _intact(bx, bu, bc, bd, bn) and _same(dd, dr) and _same(nd, ur) and _same(xd, x), n
+
+
+@pytest.mark.parametrize("n", SC_SIZES)
+def test_lincomb_edges(E, n):
+    """lincomb modes 0 - 2, into a fresh destination and in place (out aliases x)"""
+    from mock_engine import emulate_lincomb
+    g = torch.Generator().manual_seed(n % 9973 + 1)
+    x, y, z = ((torch.randn(n, generator=g) * 2).half() for _ in range(3))
+    for mode, (a, b) in ((0, (0.7312, -0.2466)), (1, (0.6123, 0.3711)), (2, (1.913, 0.0))):
+        want = torch.empty_like(x)
+        emulate_lincomb(want, x, y, z if mode == 1 else None, a, b, mode)
+        (bx, xd), (by, yd), (bz, zd), (bo, od) = _gin(x), _gin(y), _gin(z), _gout(n, torch.float16)
+        E.lincomb(od, xd, yd, zd if mode == 1 else None, a, b, mode)
+        torch.cuda.synchronize()
+        assert _intact(bx, by, bz, bo) and _same(od, want) and _same(xd, x) and _same(yd, y) and _same(zd, z), (n, mode)
+        E.lincomb(xd, xd, yd, zd if mode == 1 else None, a, b, mode)
+        torch.cuda.synchronize()
+        assert _intact(bx, by, bz) and _same(xd, want) and _same(yd, y) and _same(zd, z), (n, mode, "in place")
