@@ -124,6 +124,11 @@ SDE_PROTOTYPES = {
     "cfgpp_step_sde": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, C.POINTER(C.c_float), _I, _I, _I, _P, _S, _I, _L, _U, _P]),
 }
 
+# the DPM++ SDE extension header (include/cfgpp_dpmpp_sde.h): one stage of the two-stage stochastic step
+DPMPP_SDE_PROTOTYPES = {
+    "cfgpp_step_sde_stage": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, C.POINTER(C.c_float), _I, _I, _P, _P, _S, _I, _L, _U, _U, _P]),
+}
+
 # the MultiDiffusion panorama extension header (include/cfgpp_panorama.h): the window gather and the fused view step
 class PanoViewsC(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "C", "Hp", "Wp", "h", "w", "stride", "circular", "chunk_views")]
@@ -261,7 +266,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -21,6 +21,7 @@ SOURCES = [
     ("vpred_kernels.hip", ["-ffp-contract=off"]),    # the v-prediction twins (include/cfgpp_vpred.h): the same contract
     ("lcm_kernels.hip", ["-ffp-contract=off"]),      # the LCM step and its Philox normals (include/cfgpp_lcm.h): the same contract
     ("sde_kernels.hip", ["-ffp-contract=off"]),      # the DPM++ 2M / 3M SDE step (include/cfgpp_sde.h): the same contract, the same Philox
+    ("dpmpp_sde_kernels.hip", ["-ffp-contract=off"]),    # the DPM++ SDE stage (include/cfgpp_dpmpp_sde.h): the same contract, the same Philox
     ("pano_kernels.hip", ["-ffp-contract=off"]),     # the MultiDiffusion view step (include/cfgpp_panorama.h): the same contract
     ("norm_kernels.hip", []),
     ("small_kernels.hip", []),

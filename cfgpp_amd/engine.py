@@ -312,6 +312,48 @@ def step_sde(x: torch.Tensor, den_out: torch.Tensor, xc_out: Optional[torch.Tens
 
 
 # ----------------------------------------------------------------------------
+# DPM++ SDE (include/cfgpp_dpmpp_sde.h)
+# ----------------------------------------------------------------------------
+STAGE_D, STAGE_U, STAGE_N1, STAGE_N2 = 1, 2, 4, 8       # the bits of ``terms`` (CFGPP_STAGE_*)
+
+
+def step_sde_stage(x: torch.Tensor, base: torch.Tensor, out: torch.Tensor, den_out: torch.Tensor, xc_out: Optional[torch.Tensor],
+                   m_uc: torch.Tensor, m_c: torch.Tensor, lam: float, coef7, terms: int, last: bool, seeds=None, draw1: int = 0,
+                   draw2: int = 1, noise1: Optional[torch.Tensor] = None, noise2: Optional[torch.Tensor] = None):
+    """one stage of a DPM++ SDE step on the fp32 latents ``x`` / ``base`` [B, ...] -> ``out`` (cfgpp_step_sde_stage); ``coef7`` and
+    ``terms`` from ``dpmpp_sde.dpmpp_sde_coeffs``; each noise term that is on is ``noise1`` / ``noise2`` (fp32, x's shape) or, with
+    None, drawn in the kernel from ``seeds`` and ``draw1`` / ``draw2``.  ``base`` may be ``x``, ``out`` may be ``x``; ``xc_out`` may
+    be None."""
+    lib = _lib.load()
+    f32 = (("x", x), ("base", base), ("out", out), ("den_out", den_out)) + tuple((n, t) for n, t in (("noise1", noise1), ("noise2", noise2))
+                                                                                 if t is not None)
+    f16 = (("m_uc", m_uc), ("m_c", m_c)) + ((("xc_out", xc_out),) if xc_out is not None else ())
+    for n, t in f32 + f16:
+        _require_cuda(t, n)
+        if t.numel() != x.numel():
+            raise CfgppError(f"step_sde_stage: size mismatch ({n})")
+    if any(t.dtype != torch.float32 for _, t in f32):
+        raise CfgppError("step_sde_stage: x, base, out, den_out and the noise must be fp32")
+    if any(t.dtype != torch.float16 for _, t in f16):
+        raise CfgppError("step_sde_stage: the model output and xc_out must be fp16")
+    if len(coef7) != 7:
+        raise CfgppError("step_sde_stage: coef7 = (sigma_b, a_x, a_d, a_u, c_1, c_2, s_in)")
+    if x.dim() < 2:
+        raise CfgppError("step_sde_stage: x must be [B, ...]")
+    B = int(x.shape[0])
+    terms = int(terms)
+    sd = None
+    if not last and ((terms & STAGE_N1 and noise1 is None) or (terms & STAGE_N2 and noise2 is None)):
+        if seeds is None:
+            raise CfgppError("step_sde_stage: a noise term needs seeds or its noise tensor")
+        sd = _seed_array(seeds, B, "step_sde_stage")
+    arr = (C.c_float * 7)(*[float(v) for v in coef7])
+    check(lib.cfgpp_step_sde_stage(x.data_ptr(), base.data_ptr(), out.data_ptr(), den_out.data_ptr(), _ptr(xc_out), m_uc.data_ptr(),
+                                   m_c.data_ptr(), float(lam), arr, terms, int(bool(last)), _ptr(noise1), _ptr(noise2), sd, B,
+                                   x.numel() // B, int(draw1), int(draw2), _stream_ptr(x)), "cfgpp_step_sde_stage")
+
+
+# ----------------------------------------------------------------------------
 # MultiDiffusion panoramas (include/cfgpp_panorama.h)
 # ----------------------------------------------------------------------------
 def _pano_views_c(g, B: int, C_: int, name: str, z_pano: torch.Tensor, z_views: torch.Tensor):

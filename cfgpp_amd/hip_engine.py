@@ -279,6 +279,8 @@ class HipEngine:
     # DPM++ 2M / 3M SDE (include/cfgpp_sde.h)
     sde_input = staticmethod(E.sde_input)
     step_sde = staticmethod(E.step_sde)
+    # DPM++ SDE (include/cfgpp_dpmpp_sde.h)
+    step_sde_stage = staticmethod(E.step_sde_stage)
     # MultiDiffusion panoramas (include/cfgpp_panorama.h)
     gather_views = staticmethod(E.gather_views)
     step_ddim_views = staticmethod(E.step_ddim_views)

@@ -25,7 +25,8 @@ a_u = -a_x, and the history holds uden: the current term is den, every history t
 
 Noise.  The intervals of successive steps do not overlap, so independent standard normals per step have exactly the law of
 k-diffusion's Brownian-tree increments; they are keyed by the chains' seeds (stream id 2, draw = step index), so chain b of a batch
-reproduces chain b run alone.  ``eta=0`` is a deterministic fp32 DPM++ 2M / 3M.
+reproduces chain b run alone.  ``eta=0`` is a deterministic fp32 DPM++ 2M / 3M.  The two-stage ``dpm++_sde``, whose two noise terms
+per step DO overlap, is ``dpmpp_sde.py`` (its own registry; this one keeps refusing the name).
 
 Refused by name: zero_terminal_snr, guidance_rescale, inversion / edit / inpaint (``src_img`` / ``mask`` / ``strength``),
 ``solver_type`` on 3M, a negative or non-finite ``eta`` / ``s_noise``, a sharded run without per-rank ``seeds=``.  Graph replay is

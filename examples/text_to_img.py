@@ -64,7 +64,7 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--draw", action="store_true", help="save z0t / zt decodes every step (draw_tweedie + draw_noisy)")
     ap.add_argument("--lcm_original_steps", type=int, default=None,
                     help="--method lcm: original_inference_steps of the LCM schedule (default: the checkpoint's scheduler_config.json, else 50)")
-    ap.add_argument("--eta", type=float, default=None, help="--method dpm++_2m_sde* / dpm++_3m_sde*: noise level (default 1; 0 = deterministic)")
+    ap.add_argument("--eta", type=float, default=None, help="--method dpm++_2m_sde* / dpm++_3m_sde* / dpm++_sde*: noise level (default 1; 0 = deterministic)")
     ap.add_argument("--s_noise", type=float, default=None, help="--method dpm++_*_sde*: noise multiplier (default 1)")
     ap.add_argument("--solver_type", default=None, choices=("midpoint", "heun"), help="--method dpm++_2m_sde*: second-order form (default midpoint)")
     ap.add_argument("--sigma_schedule", default=None, choices=("karras", "exponential"), help="--method dpm++_*_sde*: sigma schedule (default karras)")
@@ -113,6 +113,9 @@ def main(argv=None, solver_kwargs=None) -> None:
             kw["lcm_original_steps"] = args.lcm_original_steps
     from cfgpp_amd.sde import get_sde_solver, sde_solver_names
     sde = args.method in sde_solver_names()      # the SDE samplers have their own registry too (cfgpp_amd/sde.py)
+    from cfgpp_amd.dpmpp_sde import dpmpp_sde_solver_names, get_dpmpp_sde_solver
+    if args.method in dpmpp_sde_solver_names():      # the two-stage DPM++ SDE sampler: the same options, its own registry again
+        sde, get_sde_solver = True, get_dpmpp_sde_solver
     if sde:
         kw.update({k: getattr(args, k) for k in ("eta", "s_noise", "solver_type", "sigma_schedule") if getattr(args, k) is not None})
     if args.model in ("sdxl", "sdxl_lightning"):
