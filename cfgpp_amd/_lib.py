@@ -97,6 +97,11 @@ LONG_PROMPT_PROTOTYPES = {
     "cfgpp_unet_set_max_tokens": (_I, [_P, _I]),
 }
 
+# the regional-prompt extension header (include/cfgpp_regions.h)
+REGIONS_PROTOTYPES = {
+    "cfgpp_unet_set_regions": (_I, [_P, _P, _I, _I]),
+}
+
 # the FreeU extension header (include/cfgpp_freeu.h)
 FREEU_PROTOTYPES = {
     "cfgpp_unet_set_freeu": (_I, [_P, _F, _F, _F, _F, _I]),
@@ -172,6 +177,7 @@ DEBUG_PROTOTYPES = {
     "cfgpp_attention_set_cross_long": (None, [_I]),
     "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
+    "cfgpp_op_attention_region": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "cfgpp_op_perceiver_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_vit": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_vit_attention_last_launch": (None, [C.POINTER(C.c_int)]),
@@ -266,7 +272,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(REGIONS_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -922,6 +922,267 @@ xattn64_long_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup 
     }
 }
 
+// ---- regional cross-attention, dp = 64: R = 2 .. 4 prompts of 77 tokens, every query attends to ONE of them ---------------
+// Keys [77 r, 77 r + 77) of the resident K / V^T are region r's prompt; ids [map_rows][q_tok_pad] (uint8, pads 0) names the region
+// of every query, and a query's result is softmax(q K_own) V_own over its own 77 keys - nothing else reaches it.  The frame is
+// xattn64_long_kernel's: ceil(77 R / 64) = 3 .. 5 tiles of (K | V^T) loaded once by LDS-DMA, xqb query blocks per workgroup, the
+// next block's Q (and region ids) prefetched, the XCD remap.  In the S^T accumulator layout a lane owns one query and its registers
+// run over the keys, so the mask is a per-lane compare: register r of sub-tile kt of tile t holds key t*64 + kt*32 + (r&3) + 8(r>>2)
+// + 4 hi, kept when (unsigned)(key - 77 rid) < 77, else -inf.  That mask covers the slots behind the context as well.
+//
+// Softmax: the ONLINE form is kept (choice, after reading the loop: an exact two-pass softmax over resident K doubles the QK^T
+// MFMAs and their LDS reads, 3 .. 5 tiles x 8 MFMAs per query block; the online form adds one register of per-lane state).  What
+// the long kernel's loop cannot do is start: a row of region r >= 1 has no own key in tile 0, its tile maximum there is -inf, and
+// the unconditional "t == 0" re-reference would give delta = -inf, alpha = +inf, NaN accumulators.  Here every lane carries
+// `seen` (an own key has been met).  Until then m_ref = 0, every P is exp2(-inf) = 0 and the accumulators stay 0.  The re-reference
+// branch is taken when a lane meets its first own key (delta = its tile maximum, alpha = 1: nothing accumulated yet) or, as in the
+// flash loop, when a seen lane's tile maximum exceeds RESCALE_THR (delta = max(mx, 0), alpha = 2^-delta); lanes that are neither
+// get delta = 0, alpha = 1 - exact.  Tiles after a row's own keys have mx = -inf: no branch, P = 0.  Every tile with a valid key is
+// multiplied for every wave: no wave-uniform skip of tiles without own keys (not measured, so not built).
+// A region id >= n_regions (refused by the engine) is clamped to n_regions - 1.
+// LDS: 48 KB (R = 2), 64 KB (R = 3), 80 KB (R = 4), as the long kernel at the same key counts: three / two / two workgroups per CU.
+// Registers (gfx950, allocation aimed at three waves per SIMD): <3, ONES> 141 VGPRs, <4, ONES> 151, <4, fp32 sum> 151 (the long
+// kernel's 135 / 144 / 142 plus the mask base, `seen` and the prefetched ids); no AGPRs, no scratch, 3 waves / SIMD.
+template <int D16, bool ONES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
+xattn64_region_kernel(const AttnArgs a, int xqb /* 128-query blocks per workgroup */, int nxb /* workgroups per batch*head */,
+                      const unsigned char* __restrict__ ids, int ids_bstride /* 0 (one map for all rows) or q_tok_pad */, int n_regions) {
+    constexpr int DP = 64, DT = 2, TILE = 64 * 128;
+    extern __shared__ __attribute__((aligned(16))) char smem[];      // (K tile t | V^T tile t) for t = 0 .. ntiles - 1
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l31 = lane & 31, hi = lane >> 5;
+    int xb, bh;
+    {   // XCD-contiguous (batch*head, chunk) order as attn_block_map
+        const int T = gridDim.x, bid = blockIdx.x;
+        const int q = T >> 3, r = T & 7, xcd = bid & 7, idx = bid >> 3;
+        const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
+        bh = w / nxb; xb = w - bh * nxb;
+    }
+    const half_t* Qb = a.q + (long)bh * a.q_tok_pad * DP;
+    const half_t* Kb = a.k + (long)bh * a.k_tok_pad * DP;
+    const half_t* Vb = a.vt + (long)bh * DP * a.k_tok_pad;
+    const int ntiles = (a.nk_valid + 63) >> 6;               // 3 .. 5 (nk_valid = 77 * n_regions)
+    const int nsub = (a.nk_valid + 31) >> 5;                 // 32-key sub-tiles with at least one valid key
+    {
+        const int r8 = lane >> 3, pc = lane & 7;
+#pragma unroll
+        for (int t = 0; t < 5; ++t) {
+            if (t < ntiles) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int row = wid * 16 + h * 8 + r8;
+                    const int lc = pc ^ ((row >> 1) & 7);
+                    if (t * 64 + wid * 16 < nsub * 32)         // (wave-uniform) K rows of a sub-tile with a valid key
+                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Kb + (long)(t * 64 + row) * DP + lc * 8),
+                                                         (__attribute__((address_space(3))) void*)(smem + t * 2 * TILE + (wid * 16 + h * 8) * 128), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(Vb + (long)row * a.k_tok_pad + t * 64 + lc * 8),
+                                                     (__attribute__((address_space(3))) void*)(smem + t * 2 * TILE + TILE + (wid * 16 + h * 8) * 128), 16, 0, 0);
+                }
+            }
+        }
+    }
+    const int fsw = (l31 >> 1) & 7;
+    const int frow = l31 * 128;
+    const int b = bh / a.heads, head = bh - b * a.heads;
+    const unsigned char* idb = ids + (long)b * ids_bstride;  // q0 + l31 < nqb * 128 <= q_tok_pad: every read is inside the row
+    // first block's Q and region ids while the DMA is in flight
+    half8_t qf[D16];
+    int q0 = (xb * xqb) * 128 + wid * 32;
+#pragma unroll
+    for (int ks = 0; ks < D16; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(Qb + (long)(q0 + l31) * DP + ks * 16 + hi * 8);
+    int ridf = idb[q0 + l31];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    for (int blk = 0; blk < xqb; ++blk) {
+        half8_t qs[D16];
+#pragma unroll
+        for (int ks = 0; ks < D16; ++ks)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) qs[ks][j] = (half_t)((float)qf[ks][j] * a.scale_log2e);
+        const int qrow = q0 + l31;
+        // the lane's own keys seen from its half-wave: key - own0 in [0, 77) with key = t*64 + kt*32 + (r&3) + 8(r>>2) + 4 hi
+        const int own0 = 77 * min(ridf, n_regions - 1) - 4 * hi;
+        // next block's Q and region ids (clamped: the last block re-reads itself)
+        const int q0n = blk + 1 < xqb ? q0 + 128 : q0;
+#pragma unroll
+        for (int ks = 0; ks < D16; ++ks) qf[ks] = *reinterpret_cast<const half8_t*>(Qb + (long)(q0n + l31) * DP + ks * 16 + hi * 8);
+        ridf = idb[q0n + l31];
+
+        f32x16 oacc[DT];
+        f32x16 negm;                 // -m_ref over the 16 accumulator registers (C operand of the first S^T MFMA of a sub-tile)
+        float l_run = 0.f;           // only used when !ONES
+        bool seen = false;           // this lane's query has met an own key: m_ref is a real reference
+#pragma unroll
+        for (int r = 0; r < 16; ++r) negm[r] = 0.f;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) oacc[i][r] = 0.f;
+
+        for (int t = 0; t < ntiles; ++t) {
+            const char* Ks = smem + t * 2 * TILE;
+            const char* Vs = Ks + TILE;
+            const int nkt = nsub - 2 * t >= 2 ? 2 : 1;       // (wave-uniform) sub-tiles of this tile with a valid key
+            // ---- S^T - m = K Q^T + (-m) for up to two 32-key sub-tiles (log2 domain), foreign keys masked ----
+            f32x16 s[2];
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                if (kt < nkt) {
+#pragma unroll
+                    for (int ks = 0; ks < D16; ++ks) {
+                        const half8_t kf = *reinterpret_cast<const half8_t*>(Ks + kt * 32 * 128 + frow + ((((ks << 1) | hi) ^ fsw) << 4));
+                        s[kt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qs[ks], ks == 0 ? negm : s[kt], 0, 0, 0);
+                    }
+                    const int rel0 = t * 64 + kt * 32 - own0;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r)
+                        s[kt][r] = (unsigned)(rel0 + ((r & 3) + 8 * (r >> 2))) < 77u ? s[kt][r] : -INFINITY;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[kt][r] = -INFINITY;   // no valid key: neither loaded nor multiplied
+                }
+            }
+            // ---- online softmax (deferred re-reference), started per lane at the first tile with an own key ----
+            float mx = s[0][0];                      // tile max RELATIVE to m_ref (-inf: no own key in this tile)
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) mx = fmaxf(mx, s[kt][r]);
+            mx = fmaxf(mx, __shfl_xor(mx, 32));
+            const bool own_here = mx > -INFINITY;
+            if (!__all(seen ? mx <= RESCALE_THR : !own_here)) {   // a first own key, or (rare) a jump: re-reference, exact
+                const float delta = seen ? fmaxf(mx, 0.f) : own_here ? mx : 0.f;
+                const float alpha = seen ? __builtin_amdgcn_exp2f(-delta) : 1.0f;      // not seen: O = 0, l = 0
+                seen = seen || own_here;
+                l_run *= alpha;
+#pragma unroll
+                for (int i = 0; i < DT; ++i)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) oacc[i][r] *= alpha;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) negm[r] -= delta;
+#pragma unroll
+                for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) s[kt][r] -= delta;
+            }
+            float psum = 0.f;
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float pv = __builtin_amdgcn_exp2f(s[kt][r]);
+                    s[kt][r] = pv;
+                    if constexpr (!ONES) psum += pv;
+                }
+            if constexpr (!ONES) l_run += psum;
+            // ---- O^T += V^T P^T ----
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt) {
+                if (kt < nkt) {
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt) {
+                        half8_t pf;
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) pf[j] = (half_t)s[kt][8 * tt + j];
+                        const int lc = kt * 4 + 2 * tt + hi;               // logical 16-B chunk of the (permuted) key axis
+#pragma unroll
+                        for (int i = 0; i < DT; ++i) {
+                            const half8_t vf = *reinterpret_cast<const half8_t*>(Vs + i * 32 * 128 + frow + ((lc ^ fsw) << 4));
+                            oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[i], 0, 0, 0);
+                        }
+                    }
+                }
+            }
+        }
+        // ---- finalize: O = O^T / l, store token-major ----
+        float l_tot;
+        if constexpr (ONES) {
+            const int dr = a.d & 31;
+            float lv = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) if (dr == 8 * g) lv = oacc[DT - 1][4 * g];
+            l_tot = __shfl(lv, l31);
+        } else {
+            l_tot = l_run + __shfl_xor(l_run, 32);
+        }
+        const float inv_l = 1.0f / l_tot;
+        if (qrow < a.nq) {
+            half_t* orow = a.o + ((long)b * a.nq + qrow) * a.o_ld + head * a.d;
+#pragma unroll
+            for (int i = 0; i < DT; ++i)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int dd = i * 32 + 8 * g + 4 * hi;
+                    if (dd < a.d) {
+                        half4_t o;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) o[k] = (half_t)(oacc[i][4 * g + k] * inv_l);
+                        *reinterpret_cast<half4_t*>(orow + dd) = o;
+                    }
+                }
+        }
+        q0 = q0n;
+    }
+}
+
+// Regional cross-attention for every other head dim (dp != 64: SD1.5's d = 80 / 160, the tiny nets' d = 32) and for dp = 64 under
+// cfgpp_attention_set_dma(0) / set_cross(0): a correctness path in the mould of attn_ip_add_kernel.  One thread per (batch*head,
+// query) runs the complete softmax over its region's 77 keys in fp32 with the rounding points of the MFMA kernels (q * d^-1/2 *
+// log2(e) to fp16, P to fp16, the denominator summed from the rounded P, V^T read through cfgpp_vt_pos) and stores fp16(O / l).
+// The 77 scores live in registers (256 VGPRs + 62 AGPRs, no scratch, one wave per SIMD: not a hot path); neighbouring threads of a
+// region read the same K rows.  A region id >= n_regions is clamped.
+__global__ void __launch_bounds__(256)
+attn_region_rows_kernel(const AttnArgs a, int dp, const unsigned char* __restrict__ ids, int ids_bstride, int n_regions) {
+    const int q = blockIdx.x * 256 + threadIdx.x, bh = blockIdx.y;
+    if (q >= a.nq) return;
+    const int b = bh / a.heads, head = bh - b * a.heads;
+    const int key0 = 77 * min((int)ids[(long)b * ids_bstride + q], n_regions - 1);
+    const half_t* Qr = a.q + ((long)bh * a.q_tok_pad + q) * dp;
+    const half_t* Kr = a.k + ((long)bh * a.k_tok_pad + key0) * dp;
+    const half_t* Vr = a.vt + (long)bh * dp * a.k_tok_pad;
+    float sc[77];
+#pragma unroll
+    for (int k = 0; k < 77; ++k) sc[k] = 0.f;
+    for (int d0 = 0; d0 < a.d; d0 += 8) {
+        const half8_t raw = *reinterpret_cast<const half8_t*>(Qr + d0);
+        float qs[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qs[j] = (float)(half_t)((float)raw[j] * a.scale_log2e);
+#pragma unroll
+        for (int k = 0; k < 77; ++k) {
+            const half8_t kf = *reinterpret_cast<const half8_t*>(Kr + (long)k * dp + d0);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) sc[k] += qs[j] * (float)kf[j];
+        }
+    }
+    float m = sc[0];
+#pragma unroll
+    for (int k = 1; k < 77; ++k) m = fmaxf(m, sc[k]);
+    float l = 0.f;
+#pragma unroll
+    for (int k = 0; k < 77; ++k) {
+        sc[k] = (float)(half_t)__builtin_amdgcn_exp2f(sc[k] - m);
+        l += sc[k];
+    }
+    const float inv_l = 1.0f / l;
+    half_t* orow = a.o + ((long)b * a.nq + q) * a.o_ld + head * a.d;
+    for (int d0 = 0; d0 < a.d; d0 += 4) {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 77; ++k) {
+            const int col = cfgpp_vt_pos(key0 + k);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += sc[k] * (float)Vr[(long)(d0 + j) * a.k_tok_pad + col];
+        }
+        half4_t o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = (half_t)(acc[j] * inv_l);
+        *reinterpret_cast<half4_t*>(orow + d0) = o;
+    }
+}
+
 template <int D16, bool ONES, int NST, int WPE = 3>
 int launch_attn64(const AttnArgs& a, dim3 grid, hipStream_t s) {
     constexpr int smem = NST * 2 * 64 * 128;
@@ -1250,6 +1511,64 @@ int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o,
     hipLaunchKernelGGL(attn_ip_add_kernel, dim3(cdiv(nq, 256), BH), dim3(256), 0, s, a, dt * 32, n_img, ip_scale);
     CFGPP_HIP_CHECK(hipGetLastError());
     attn_note(5, d16, ones, 0);
+    return 0;
+}
+
+// Regional cross-attention: n_regions = 2 .. 4 prompts of 77 tokens in key slots [77 r, 77 r + 77) of buffers laid out as for
+// cfgpp_op_attention_cross (nk = 77 * n_regions); ids is a DEVICE uint8 [map_rows][q_tok_pad] (map_rows = 1: one map for every batch
+// row, or B; pads 0) and query p of row b answers with softmax(q K_own) V_own over the 77 keys of region ids[b][p] alone.  Slots
+// [77 * n_regions, k_tok_pad) may hold anything finite.  Head dims padded to 64 with the default switches: xattn64_region_kernel
+// (record: kernel 7, with its xqb).  Every other head dim, or dp = 64 under cfgpp_attention_set_dma(0) / set_cross(0):
+// attn_region_rows_kernel (record: kernel 8, xqb 0).
+int cfgpp_op_attention_region(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int n_regions,
+                              const void* ids, int map_rows, int q_tok_pad, int k_tok_pad, void* stream) {
+    attn_note(0, 0, 0, 0);
+    CFGPP_REQUIRE(q && k && vt && o, "attention_region: null pointer");
+    CFGPP_REQUIRE(ids, "attention_region: null ids (a device uint8 [map_rows][q_tok_pad] region map)");
+    CFGPP_REQUIRE(B > 0 && heads > 0 && nq > 0, "attention_region: B=%d heads=%d nq=%d", B, heads, nq);
+    CFGPP_REQUIRE(n_regions >= 2 && n_regions <= 4, "attention_region: n_regions=%d (2 .. 4 regions of 77 keys)", n_regions);
+    CFGPP_REQUIRE(map_rows == 1 || map_rows == B, "attention_region: map_rows=%d (1 or B=%d)", map_rows, B);
+    CFGPP_REQUIRE(d > 0 && d <= 160 && d % 8 == 0, "attention_region: head dim %d unsupported (multiple of 8, <= 160)", d);
+    CFGPP_REQUIRE(q_tok_pad % 128 == 0 && q_tok_pad >= nq, "attention_region: q_tok_pad=%d (nq=%d) must be a multiple of 128", q_tok_pad, nq);
+    const int nk = 77 * n_regions, need = (nk + 63) / 64 * 64;
+    CFGPP_REQUIRE(k_tok_pad % 64 == 0 && k_tok_pad >= need, "attention_region: k_tok_pad=%d must be a multiple of 64 and >= %d (n_regions=%d: %d keys)",
+                  k_tok_pad, need, n_regions, nk);
+    AttnArgs a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.o = (half_t*)o;
+    a.heads = heads; a.d = d; a.nq = nq; a.nk_valid = nk; a.q_tok_pad = q_tok_pad; a.k_tok_pad = k_tok_pad;
+    a.o_ld = heads * d;
+    a.scale_log2e = (1.0f / sqrtf((float)d)) * 1.4426950408889634f;
+    a.nqb = cdiv(nq, 128);
+    a.stagger = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int d16 = (d + 15) / 16, dt = (d + 31) / 32, BH = B * heads;
+    const bool ones = (d % 32) != 0;
+    const unsigned char* idp = (const unsigned char*)ids;
+    const int ids_bstride = map_rows == 1 ? 0 : q_tok_pad;
+    if (dt == 2 && g_attn_dma && g_attn_cross) {
+        int xqb = 1;        // the walk of cfgpp_op_attention's cross-attention branch
+        while (xqb < 8 && a.nqb % (xqb * 2) == 0 && (long)BH * (a.nqb / (xqb * 2)) >= 512) xqb *= 2;
+        const int nxb = a.nqb / xqb;
+        constexpr int kMaxSmem = 5 * 2 * 64 * 128;
+        static bool attr_set = false;
+        if (!attr_set) {
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_region_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_region_kernel<4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+            CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(xattn64_region_kernel<4, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxSmem));
+            attr_set = true;
+        }
+        const int smem = ((nk + 63) >> 6) * 2 * 64 * 128;      // <= k_tok_pad * 256 bytes: every tile the DMA reads lies inside the buffers
+        const dim3 xg(BH * nxb);
+        if (d16 == 3) hipLaunchKernelGGL((xattn64_region_kernel<3, true>), xg, dim3(256), smem, s, a, xqb, nxb, idp, ids_bstride, n_regions);
+        else if (ones) hipLaunchKernelGGL((xattn64_region_kernel<4, true>), xg, dim3(256), smem, s, a, xqb, nxb, idp, ids_bstride, n_regions);
+        else hipLaunchKernelGGL((xattn64_region_kernel<4, false>), xg, dim3(256), smem, s, a, xqb, nxb, idp, ids_bstride, n_regions);
+        CFGPP_HIP_CHECK(hipGetLastError());
+        attn_note(7, d16, ones, xqb);
+        return 0;
+    }
+    hipLaunchKernelGGL(attn_region_rows_kernel, dim3(cdiv(nq, 256), BH), dim3(256), 0, s, a, dt * 32, idp, ids_bstride, n_regions);
+    CFGPP_HIP_CHECK(hipGetLastError());
+    attn_note(8, d16, ones, 0);
     return 0;
 }
 

@@ -86,7 +86,8 @@ int cfgpp_op_attention_cross(const void* q, const void* k, const void* vt, void*
  * everywhere, 2 the resident-K/V kernel for its whole scope (the kernel's tests, the A/B measurement) */
 void cfgpp_attention_set_cross_long(int mode);
 /* test hook: what the last cfgpp_op_attention call dispatched, a host-side record: out4 = {kernel (0 nothing launched: the call
- * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel, 6 xattn64_long_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
+ * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel, 6 xattn64_long_kernel,
+ * 7 xattn64_region_kernel, 8 attn_region_rows_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
  * from the ones row of V^T), xqb (128-query blocks per workgroup of xattn64_kernel, 0 for the flash kernels)} */
 void cfgpp_attention_last_launch(int* out4);
 /* zero key slots [slot0, slot0 + n) of k [BH][tok_pad][dp] and of rows < d of vt [BH][dp][tok_pad] (the ones row stays) */
@@ -100,6 +101,16 @@ int cfgpp_op_attention_clear_slots(void* k, void* vt, int BH, int d, int tok_pad
  * in between.  ip_scale == 0: the text-only call.  Refused, nothing launched: nk_text > 96, n_img > 32, k_tok_pad < 128. */
 int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int nk_text,
                           int n_img, float ip_scale, int q_tok_pad, int k_tok_pad, void* stream);
+/* Regional cross-attention (include/cfgpp_regions.h): n_regions = 2 .. 4 prompts of 77 tokens in key slots [77 r, 77 r + 77) of
+ * buffers laid out as for cfgpp_op_attention_cross (nk = 77 * n_regions); ids is a DEVICE uint8 [map_rows][q_tok_pad] with map_rows
+ * = 1 or B and zero pads (never read past q_tok_pad), and query p of batch row b answers with softmax(q K_own) V_own over the 77
+ * keys of region ids[b][p] alone.  Slots [77 * n_regions, k_tok_pad) may hold anything finite.  last_launch kernel 7
+ * (xattn64_region_kernel: head dims padded to 64, K / V^T resident, online softmax started per lane at its first own key) or
+ * kernel 8 (attn_region_rows_kernel: every other head dim, and dp = 64 under set_dma(0) / set_cross(0); one thread per row).
+ * Refused by name, nothing launched: n_regions outside 2 .. 4, k_tok_pad < round_up(77 * n_regions, 64), map_rows not 1 or B,
+ * null ids. */
+int cfgpp_op_attention_region(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int n_regions,
+                              const void* ids, int map_rows, int q_tok_pad, int k_tok_pad, void* stream);
 /* Perceiver attention of the IP-Adapter "plus" Resampler (include/cfgpp_ip_plus.h; csrc/resampler.hip), head dim 64:
  *   o[r][j][h*64 ..] = fp16( softmax_k(q[r][j][h] . k[r][k][h] / 8) v[r][k][h] ),  ONE softmax over the S keys of kv_x followed by the
  *   n_q keys of kv_l.

@@ -12,6 +12,7 @@
 #include "engine_base.h"
 #include "../../include/cfgpp_ip_plus.h"
 #include "../../include/cfgpp_lcm.h"
+#include "../../include/cfgpp_regions.h"
 #include "freeu.h"
 
 struct cfgpp_unet : EngineBase {
@@ -63,6 +64,13 @@ struct cfgpp_unet : EngineBase {
     int max_tokens = 77;
     const half_t* ctx_text = nullptr; const float* ctx_tids = nullptr; int ctx_cond_rows = 0;
     bool ctx_set = false;
+    // ---- regional prompts (include/cfgpp_regions.h: cfgpp_unet_set_regions).  regions = 0: off, the plain engine.  regions = R =
+    // 2 .. 4: the context holds R chunks of 77 tokens and every cross-attention op calls cfgpp_op_attention_region with the region
+    // map of its level - uint8 [region_map_rows][q_pad of the level], pads 0, in buffers finalize allocates when max_tokens > 77
+    // (d_region_ids[level], max_rows x q_pad bytes each) and set_regions fills from the host, once per job.
+    int regions = 0, region_map_rows = 0;
+    unsigned char* d_region_ids[4] = {nullptr, nullptr, nullptr, nullptr};
+    int region_h[4] = {0, 0, 0, 0}, region_w[4] = {0, 0, 0, 0};
 
     // time-embedding scratch
     float* d_sin_t = nullptr; float* d_emb_h = nullptr; float* d_emb_t = nullptr; float* d_emb = nullptr;
@@ -138,8 +146,9 @@ struct cfgpp_unet : EngineBase {
         for (const IpBlock& b : ip_blocks) {
             const double per_key = 2.0 * (double)b.nheads * b.tok * b.d;
             const std::string desc = "cross_attn heads=" + std::to_string(b.nheads) + " N=" + std::to_string(b.tok) + " d=" + std::to_string(b.d);
-            plan_macs[b.plan_idx] = per_key * (ctx_tokens + ip_n_img);
+            plan_macs[b.plan_idx] = regions ? per_key * 77 : per_key * (ctx_tokens + ip_n_img);      // a regional row attends to its own 77 keys
             plan_desc[b.plan_idx] = on ? desc + " ip=" + std::to_string(n_img) : ctx_tokens != 77 ? desc + " keys=" + std::to_string(ctx_tokens) : desc;
+            if (regions) plan_desc[b.plan_idx] += " regions=" + std::to_string(regions);
         }
     }
     // the profiler's tags of the cross-attention ops follow the token count of the current context
@@ -450,6 +459,11 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                 u->hvt[i] = (half_t*)u->dmalloc((size_t)R * c.num_heads[i] * dp * round_up((int)tok, 64) * 2);
                 CFGPP_REQUIRE(u->hq[i] && u->hk[i] && u->hvt[i], "finalize: hipMalloc failed");
                 if (cfgpp_op_attention_prepare_vt(u->hvt[i], R * c.num_heads[i], d, round_up((int)tok, 64), nullptr)) return -1;
+                u->region_h[i] = H; u->region_w[i] = W;
+                if (u->max_tokens > 77) {       // the region maps of this level (cfgpp_unet_set_regions): sized here, nothing allocated later
+                    u->d_region_ids[i] = (unsigned char*)u->dmalloc((size_t)R * round_up((int)tok, 128));
+                    CFGPP_REQUIRE(u->d_region_ids[i], "finalize: hipMalloc failed");
+                }
             }
             if (i != L - 1) { H /= 2; W /= 2; }
         }
@@ -659,6 +673,9 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                 u->attn_macs_per_row += 2.0 * (double)nheads * tok * 77 * d;
                 half_t* hq = HQ; half_t* o = u->tok_attn;
                 u->plan.push_back([=](hipStream_t s, int rows) {
+                    if (uu->regions)        // regional prompts: every query attends to the 77 keys of its region, ONE launch, same launch count
+                        return cfgpp_op_attention_region(hq, ck, cvt, o, rows, nheads, d, tok, uu->regions, uu->d_region_ids[lvl],
+                                                         uu->region_map_rows == 1 ? 1 : rows, q_pad, ck_pad, s);
                     if (uu->ip_active)      // IP-Adapter: text + image keys in ONE launch (head dims padded to 64), same launch count
                         return cfgpp_op_attention_ip(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, uu->ip_n_img, uu->ip_scale, q_pad,
                                                      ck_pad, s);
@@ -871,6 +888,64 @@ int cfgpp_unet_set_max_tokens(cfgpp_unet* u, int max_tokens) {
     CFGPP_REQUIRE(max_tokens == 77 || max_tokens == 154 || max_tokens == 231 || max_tokens == 308,
                   "set_max_tokens: max_tokens=%d (77, 154, 231 or 308)", max_tokens);
     u->max_tokens = max_tokens;
+    return 0;
+}
+
+// Regional prompts (include/cfgpp_regions.h).  The level maps are nearest downsamples of the level-0 map, id_l[y][x] = id_0[y << l][x << l]
+// (what F.interpolate(mode="nearest") gives for these integer factors), made on the host and copied into the buffers finalize sized.
+int cfgpp_unet_set_regions(cfgpp_unet* u, const unsigned char* ids_host, int map_rows, int n_regions) {
+    CFGPP_REQUIRE(u && u->finalized, "set_regions: the engine is not finalized");
+    if (!ids_host && map_rows == 0 && n_regions == 0) {        // off: the plain engine
+        if (u->regions) { u->regions = 0; u->region_map_rows = 0; u->retag_cross(); }
+        return 0;
+    }
+    CFGPP_REQUIRE(!u->control, "set_regions: a ControlNet-mode engine takes no regional prompts (regions with ControlNet are not built)");
+    CFGPP_REQUIRE(u->ip_kind == cfgpp_unet::IP_NONE && !u->ip_active, "set_regions: an IP-Adapter is loaded (regions with an IP-Adapter are not built: "
+                  "its image slots sit at key 96 of the text buffers)");
+    CFGPP_REQUIRE(n_regions >= 2 && n_regions <= 4, "set_regions: n_regions=%d (2 .. 4; (NULL, 0, 0) turns regions off)", n_regions);
+    CFGPP_REQUIRE(ids_host, "set_regions: null region map");
+    CFGPP_REQUIRE(u->max_tokens >= 77 * n_regions, "set_regions: n_regions=%d needs max_tokens >= %d, the engine was built with max_tokens=%d "
+                  "(cfgpp_unet_set_max_tokens before finalize)", n_regions, 77 * n_regions, u->max_tokens);
+    CFGPP_REQUIRE(map_rows == 1 || (map_rows >= 1 && map_rows <= u->cfg.max_rows && (!u->ctx_set || map_rows == u->ctx_rows)),
+                  "set_regions: map_rows=%d (1, or the context's row count %d)", map_rows, u->ctx_set ? u->ctx_rows : u->cfg.max_rows);
+    const int H0 = u->cfg.sample_h, W0 = u->cfg.sample_w;
+    for (long i = 0; i < (long)map_rows * H0 * W0; ++i)
+        if (ids_host[i] >= n_regions) {
+            cfgpp_set_error("set_regions: region id %d at row %ld, pixel (%ld, %ld) but n_regions=%d (ids are 0 .. n_regions - 1)", (int)ids_host[i],
+                            i / ((long)H0 * W0), (i / W0) % H0, i % W0, n_regions);
+            return -2;
+        }
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    CFGPP_HIP_CHECK(hipDeviceSynchronize());                   // no forward in flight reads the maps that are rewritten below
+    std::vector<unsigned char> lvl_map;
+    for (int l = 0; l < u->cfg.num_levels; ++l) {
+        if (!u->d_region_ids[l]) continue;
+        const int h = u->region_h[l], w = u->region_w[l], q_pad = round_up(h * w, 128);
+        const int fy = H0 / h, fx = W0 / w;
+        lvl_map.assign((size_t)map_rows * q_pad, 0);
+        for (int r = 0; r < map_rows; ++r)
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x)
+                    lvl_map[(size_t)r * q_pad + y * w + x] = ids_host[((size_t)r * H0 + (size_t)y * fy) * W0 + (size_t)x * fx];
+        CFGPP_HIP_CHECK(hipMemcpy(u->d_region_ids[l], lvl_map.data(), lvl_map.size(), hipMemcpyHostToDevice));
+    }
+    u->regions = n_regions; u->region_map_rows = map_rows;
+    u->retag_cross();
+    return 0;
+}
+
+// what a forward / profile needs of the regional state (by name, with both numbers)
+static int regions_ready(const cfgpp_unet* u, int rows, const char* who) {
+    if (!u->regions) return 0;
+    if (u->ctx_tokens != 77 * u->regions) {
+        cfgpp_set_error("%s: regions are on with n_regions=%d (a context of %d tokens) but the context has tokens=%d", who, u->regions, 77 * u->regions,
+                        u->ctx_tokens);
+        return -2;
+    }
+    if (u->region_map_rows != 1 && u->region_map_rows != rows) {
+        cfgpp_set_error("%s: the region map was set for map_rows=%d, the call runs rows=%d (1 or rows)", who, u->region_map_rows, rows);
+        return -2;
+    }
     return 0;
 }
 
@@ -1376,7 +1451,8 @@ int cfgpp_unet_forward(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
     CFGPP_REQUIRE(!u->control || u->img_rows > 0, "forward: ControlNet without a control image (call cfgpp_unet_image_condition first)");
     CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "forward: the image context (IP-Adapter) was set for %d rows, the forward runs %d: call "
                   "cfgpp_unet_image_context after cfgpp_unet_set_context", u->ip_rows, rows);
-    if (u->ctrl && u->ctrl_scale != 0.f) {          // the attached ControlNet's forward first: its residuals feed this plan
+    if (int e = regions_ready(u, rows, "forward")) return e;
+    if (u->ctrl && u->ctrl_scale != 0.f) {         // the attached ControlNet's forward first: its residuals feed this plan
         cfgpp_unet* cn = u->ctrl;
         CFGPP_REQUIRE(cn->img_rows > 0, "forward: a ControlNet is attached but has no control image (cfgpp_unet_image_condition)");
         CFGPP_REQUIRE(cn->ctx_set && cn->ctx_rows == rows, "forward: the attached ControlNet's context is set for %d rows, the forward runs %d",
@@ -1413,6 +1489,8 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
     CFGPP_REQUIRE(rows == u->ctx_rows && rows <= u->cfg.max_rows, "sample_graph: rows=%d but context was set for %d rows", rows, u->ctx_rows);
     CFGPP_REQUIRE(!u->ctrl && !u->control, "sample_graph: a ControlNet is attached (a controlled step is not captured): detach it "
                                             "(cfgpp_unet_attach_control(u, NULL, 0)) or run the eager loop");
+    CFGPP_REQUIRE(!u->regions, "sample_graph: regional prompts are on (cfgpp_unet_set_regions, n_regions=%d): a region-masked step is not captured, "
+                                "run the eager loop", u->regions);
     hipStream_t s = (hipStream_t)stream;
     CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
                   "sample_graph: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",
@@ -1504,6 +1582,7 @@ int cfgpp_unet_profile(cfgpp_unet* u, const void* z, int z_is_half, int z_rows, 
     CFGPP_REQUIRE(!u->time_cond || u->time_cond_set, "profile: a guidance-embedded UNet (time_cond_proj_dim=%d) needs "
                   "cfgpp_unet_guidance_embedding first", u->time_cond);
     CFGPP_REQUIRE(!u->ip_active || u->ip_rows == rows, "profile: the image context (IP-Adapter) was set for %d rows", u->ip_rows);
+    if (int e = regions_ready(u, rows, "profile")) return e;
     u->in_z = z; u->in_z_half = z_is_half; u->in_z_rows = z_rows; u->in_t = t; u->out_eps = eps_out;
     hipStream_t s = (hipStream_t)stream;
     const size_t n = u->plan.size();
@@ -1571,7 +1650,8 @@ double cfgpp_unet_flops(cfgpp_unet* u, int rows) {
     // the prefix a CFG call shares is computed once for both halves: counted once when the most recent forward shared it
     const double once = u->ran_shared == 1 ? u->prefix_macs_per_row * (rows / 2) : 0.0;
     const double ip = u->ip_active ? u->ip_macs_per_key * u->ip_n_img : 0.0;      // the image keys, while an adapter is active
-    const double text = u->ip_macs_per_key * (u->ctx_tokens - 77);      // attn_macs_per_row counts 77 text keys per cross-attention
+    // attn_macs_per_row counts 77 text keys per cross-attention; a regional row attends to its own 77 keys
+    const double text = u->regions ? 0.0 : u->ip_macs_per_key * (u->ctx_tokens - 77);
     return 2.0 * ((u->macs_per_row + u->attn_macs_per_row + text + ip) * rows - once);
 }
 

@@ -532,6 +532,26 @@ class HipUNet:
         check(self.lib.cfgpp_unet_set_context(self._h, ehs.data_ptr(), rows, tokens, _ptr(te), _ptr(ti), cond_rows,
                                               _stream_ptr(ehs)), "cfgpp_unet_set_context")
 
+    def set_regions(self, ids: Optional[torch.Tensor], n_regions: int = 0):
+        """regional prompts on the finalized engine (include/cfgpp_regions.h: cfgpp_unet_set_regions): ``ids`` is an integer region
+        map [1 or rows, H, W] with ids < ``n_regions`` = 2 .. 4, and the context to follow holds ``n_regions`` chunks of 77 tokens.
+        ``None`` turns regions off: the plain engine.  The map is copied into the engine's own buffers, once per call."""
+        if ids is None:
+            check(self.lib.cfgpp_unet_set_regions(self._h, None, 0, 0), "cfgpp_unet_set_regions")
+            self.regions = 0
+            return self
+        ids = torch.as_tensor(ids)
+        if ids.dim() == 2:
+            ids = ids[None]
+        if ids.dim() != 3 or tuple(ids.shape[1:]) != (self.H, self.W):
+            raise CfgppError(f"set_regions: region map of shape {tuple(ids.shape)}, expected [1 or rows, {self.H}, {self.W}]")
+        if ids.is_floating_point() or int(ids.min()) < 0 or int(ids.max()) > 255:
+            raise CfgppError("set_regions: the region map must hold integer ids 0 .. n_regions - 1")
+        host = ids.detach().to("cpu", torch.uint8).contiguous()
+        check(self.lib.cfgpp_unet_set_regions(self._h, host.data_ptr(), int(host.shape[0]), int(n_regions)), "cfgpp_unet_set_regions")
+        self.regions = int(n_regions)
+        return self
+
     def image_condition(self, cond: torch.Tensor):
         """inpaint UNets only: the step-invariant extra input channels ``cond`` [1 or z_rows, in - out, H, W] (mask, masked-image
         latent: diffusers' channel order), copied into the engine (include/cfgpp.h: cfgpp_unet_image_condition)."""

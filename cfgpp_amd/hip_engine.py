@@ -66,6 +66,7 @@ class HipEngine:
         self._lora = LoraState(cfg, self.unet.lora)
         self._control = None         # (HipControlNet, scale) while a control is set
         self._ip = None              # the parsed IP-Adapter while one is loaded
+        self._regions = 0            # n_regions while a region map is set (set_regions)
         self._eps = None
         self._g_buf = None
         # opt-in guard for the first runs with a real checkpoint (real SDXL activations approach the fp16 maximum in the deep
@@ -173,6 +174,32 @@ class HipEngine:
         else:
             self.unet.set_image_context(assemble_embeds(embeds, negative, self.B), float(scale))
 
+    # -- regional prompts ---------------------------------------------------------------
+    def set_regions(self, ids: Optional[torch.Tensor], n_regions: int = 0):
+        """region map ``ids`` [1 or B, H, W] (integer ids < ``n_regions`` = 2 .. 4) for the contexts to follow, whose uc / c hold
+        ``n_regions`` chunks of 77 tokens; None: off, the plain engine (include/cfgpp_regions.h: cfgpp_unet_set_regions).  The
+        unconditional rows use the same map: a [B, H, W] map is laid out for the rows [uc_1..uc_B, c_1..c_B].  While regions
+        are on the loops stay eager."""
+        if ids is None:
+            if self._regions:
+                self.unet.set_regions(None)
+            self._regions = 0
+            return self
+        if self._control is not None:
+            raise CfgppError("set_regions: a ControlNet is set (control_image with regions is not built)")
+        if self._ip is not None:
+            raise CfgppError("set_regions: an IP-Adapter is loaded (ip_adapter with regions is not built)")
+        ids = torch.as_tensor(ids)
+        if ids.dim() == 3 and int(ids.shape[0]) > 1:
+            ids = torch.cat([ids, ids], 0)
+        self.unet.set_regions(ids, int(n_regions))
+        self._regions = int(n_regions)
+        return self
+
+    @property
+    def regions(self) -> int:
+        return self._regions
+
     # -- FreeU -----------------------------------------------------------------------
     def set_freeu(self, spec):
         """``(s1, s2, b1, b2)`` (diffusers ``enable_freeu``; a mapping with those keys works too) or None (off: the plain engine, bit
@@ -229,7 +256,8 @@ class HipEngine:
     @property
     def graph_enabled(self) -> bool:
         """$CFGPP_GRAPH=1: DDIM loops without a callback run as hipGraph replays of one captured step (default off: see DESIGN.md)"""
-        return os.environ.get("CFGPP_GRAPH", "0") not in ("", "0") and self._control is None     # a controlled step is not captured
+        # a controlled step is not captured, nor a region-masked one
+        return os.environ.get("CFGPP_GRAPH", "0") not in ("", "0") and self._control is None and not self._regions
 
     def ddim_loop_graph(self, zt: torch.Tensor, steps, lam: float, tweedie_uc: bool, renoise_uc: bool, single: str = ""):
         """run the whole loop on (a persistent copy of) ``zt``; returns (z0t, zt) as fresh tensors.  ``single``: "uc" / "c" when the

@@ -64,6 +64,9 @@ def controlled(sample):
         if any(v is not None for v in ip.values()) and not self.controllable:
             raise ValueError(f"{type(self).__name__}.sample() does not take ip_adapter_image_embeds / ip_adapter_image: IP-Adapter image "
                              "prompts are for the text-to-image solvers (inversion, edit and inpaint solvers refuse them)")
+        # sample(..., region_prompts=[p1, ..], region_masks=[m1, ..]): regional prompts (cfgpp_amd/regions.py); empty = the plain call
+        if "region_prompts" in kwargs or "region_masks" in kwargs:
+            self._region_job = self._regions_prepare(kwargs.pop("region_prompts", None), kwargs.pop("region_masks", None), image, ip)
         self._ip_job = self._ip_prepare(ip, ip_scale)
         lora_scale = kwargs.pop("lora_scale", None)
         if lora_scale is not None:          # shorthand: every adapter of the solver at this scale, from this job on
@@ -80,6 +83,7 @@ def controlled(sample):
         finally:
             self._ip_job = None
             self._job_rescale = None
+            self._region_job = None
     return run
 
 
@@ -119,6 +123,22 @@ class StableDiffusion:
         if self.max_prompt_chunks > 1 and kwargs.get("ip_adapter") is not None:
             raise ValueError(f"ip_adapter=... together with max_prompt_chunks={self.max_prompt_chunks} is not supported: the IP-Adapter's "
                              "image tokens sit at key 96 of a 128-slot cross-attention buffer (max_prompt_chunks must be 1)")
+        # regional prompts (cfgpp_amd/regions.py): 1 = off (no new call anywhere); R = 2 .. 4: sample() takes up to R - 1 region
+        # prompts with their masks, and the engine is built for text contexts of 77 * R tokens
+        self.max_regions = int(kwargs.get("max_regions", 1))
+        self._region_job = None
+        self._region_serial = 0
+        if not 1 <= self.max_regions <= 4:
+            raise ValueError(f"max_regions={self.max_regions}: 1 (off) .. 4")
+        if self.max_regions > 1:
+            if self.max_prompt_chunks > 1:
+                raise ValueError(f"max_regions={self.max_regions} together with max_prompt_chunks={self.max_prompt_chunks} is not supported: "
+                                 "region prompts are plain 77-token prompts (long region prompts are not built)")
+            if kwargs.get("ip_adapter") is not None:
+                raise ValueError(f"max_regions={self.max_regions} together with ip_adapter=... is not supported (IP-Adapter with regions is not built)")
+            if not self.controllable:
+                raise ValueError(f"max_regions={self.max_regions}: {type(self).__name__} takes no regional prompts - they are for the "
+                                 "text-to-image solvers (inversion, edit, inpaint and panorama solvers refuse them)")
 
         # what the UNet predicts and on which schedule (DESIGN.md "v-prediction"): "epsilon" / "leading" / no rescaling are the
         # reference's models, bit for bit
@@ -153,7 +173,7 @@ class StableDiffusion:
             from .hip_engine import HipEngine
             engine = HipEngine(cfg, max_batch=self.max_batch, latent_hw=self.latent_hw, device=device,
                                weights=kwargs.get("unet_weights", "synthetic"), weight_seed=kwargs.get("weight_seed", 0),
-                               max_tokens=77 * self.max_prompt_chunks)
+                               max_tokens=77 * max(self.max_prompt_chunks, self.max_regions))
         self.engine = engine
         self.unet = engine
         self.work_device = getattr(engine, "device", torch.device("cpu"))
@@ -458,10 +478,22 @@ class StableDiffusion:
         b = uc if c is None else c
         extra, extra_key = self._added_context(added)
         key = (a.data_ptr(), b.data_ptr(), tuple(a.shape), tuple(b.shape), a._version, b._version, self._lora_epoch(), *extra_key)
+        job = self._region_job
+        if self.max_regions > 1:
+            key = (*key, job.serial if job is not None else 0)
         changed = getattr(self, "_ctx_key", None) != key
         if changed:
             self._refuse_long_context_when_sharded(max(int(a.shape[1]), int(b.shape[1])))      # (prompt_embeds= comes this way too)
-            self._set_context(a, b, *extra)
+            if job is not None:         # regional prompts: the stacked context, then the map the cross-attentions select by
+                from .regions import stack_context
+                sa = stack_context(a, None, job.embeds)[0] if uc is not None else stack_context(None, a, job.embeds)[1]
+                sb = stack_context(None, b, job.embeds)[1] if c is not None else stack_context(b, None, job.embeds)[0]
+                self._set_context(sa, sb, *extra)
+                self.engine.set_regions(job.ids, job.n_regions)
+            else:
+                self._set_context(a, b, *extra)
+                if self.max_regions > 1 and getattr(self.engine, "regions", 0):
+                    self.engine.set_regions(None)
             self._ctx_key = key
             self._ctx_keep = (a, b, *extra)
         self._ensure_image_context(changed, uc, c)
@@ -469,6 +501,41 @@ class StableDiffusion:
     def _added_context(self, added):
         """-> (tensors that travel with the text context, what they add to the cache key): none for SD1.5"""
         return (), ()
+
+    # ------------------------------------------------------------------ regional prompts (cfgpp_amd/regions.py)
+    def _region_hidden(self, prompt):
+        """hidden states [1 or B, 77, D] of one region prompt: a plain 77-token prompt, through every text tower alike"""
+        towers = self.text_encoder if isinstance(self.text_encoder, (tuple, list)) else (self.text_encoder,)
+        return torch.cat([enc(as_list(prompt))[0] for enc in towers], dim=-1).to(self.work_device, torch.float16)
+
+    def _regions_prepare(self, region_prompts, region_masks, control_image=None, ip=None):
+        """the region job of one sample() call, or None for a plain call (empty lists): refusals by name, the region map, the
+        region prompts' hidden states"""
+        from . import regions as RG
+        R = RG.check_lists(region_prompts, region_masks, self.max_regions if self.max_regions > 1 else RG.MAX_REGIONS)
+        if R == 1:
+            return None
+        if not self.controllable:
+            raise ValueError(f"{type(self).__name__}.sample() does not take region_prompts: regional prompts are for the text-to-image "
+                             "solvers (inversion, edit, inpaint and panorama solvers refuse them)")
+        if self.max_regions < 2:
+            raise ValueError(f"region_prompts given, but the solver was built with max_regions={self.max_regions}: "
+                             "get_solver(..., max_regions=R) with R = 2 .. 4 sizes the engine for R regions")
+        if control_image is not None:
+            raise ValueError("control_image together with region_prompts is not supported (ControlNet with regions is not built)")
+        if ip is not None and any(v is not None for v in ip.values()):
+            raise ValueError("ip_adapter_image / ip_adapter_image_embeds together with region_prompts is not supported (IP-Adapter with regions is not built)")
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("region_prompts in a sharded run (world size > 1) is not supported: the packed broadcast of the conditioning "
+                             "has the shapes of one 77-token chunk")
+        if not hasattr(self.engine, "set_regions"):
+            raise ValueError(f"region_prompts: the engine {type(self.engine).__name__} has no set_regions")
+        embeds = tuple(self._region_hidden(p) for p in region_prompts)
+        B = max(int(e.shape[0]) for e in embeds)
+        ids = RG.build_region_map(list(region_masks), self.latent_hw, B if B > 1 else None)     # (B = 1: the engine checks the rows)
+        self._region_serial += 1
+        return RG.RegionJob(ids, embeds, self._region_serial)
 
     # ------------------------------------------------------------------ the DDIM step rule; whole-loop graph replay
     def _ddim_step_coeffs(self, t, inversion: bool, wrap: bool):

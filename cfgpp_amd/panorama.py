@@ -159,6 +159,9 @@ class _PanoramaMixin:
                 what = "ControlNet conditioning" if k == "control_image" else "IP-Adapter image prompts"
                 raise ValueError(f"{type(self).__name__}.sample() does not take {k}: {what} per view are not supported by the panorama "
                                  "solvers")
+        if kwargs.get("region_prompts") or kwargs.get("region_masks"):
+            raise ValueError(f"{type(self).__name__}.sample() does not take region_prompts: regional prompts per view are not supported by "
+                             "the panorama solvers")
         if kwargs.get("guidance_rescale"):
             self._check_guidance_rescale(kwargs["guidance_rescale"])
         import torch.distributed as dist

@@ -54,6 +54,10 @@ def main(argv=None, solver_kwargs=None) -> None:
     ap.add_argument("--max_prompt_chunks", type=int, default=1, choices=(1, 2, 3, 4),
                     help="2 .. 4: prompts of up to 75 ids per chunk with (emphasis:1.3) / [de-emphasis] / BREAK, the engine built for "
                          "77 x K text tokens (cfgpp_amd/prompt.py); 1 (default): prompts cut at 75 ids, brackets literal")
+    ap.add_argument("--max_regions", type=int, default=1, choices=(1, 2, 3, 4),
+                    help="regional prompts: size the engine for up to this many regions (the prompt is region 0; 1 = off)")
+    ap.add_argument("--region", action="append", default=[], metavar="X0,Y0,X1,Y1:PROMPT",
+                    help="repeatable: a rectangle as fractions of width and height, and the prompt that applies inside it (later ones win)")
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--ip_adapter", default=None, metavar="PATH[:SCALE]",
@@ -102,6 +106,8 @@ def main(argv=None, solver_kwargs=None) -> None:
     vpred.cli_kwargs(args, kw)        # explicit flags win over the checkpoint's files
     if args.max_prompt_chunks > 1:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
+    if args.max_regions > 1:
+        kw["max_regions"] = args.max_regions
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference
@@ -124,18 +130,29 @@ def main(argv=None, solver_kwargs=None) -> None:
                   else get_solver(args.method, **kw))
         result = solver.sample(prompt1=[args.null_prompt, prompts], prompt2=[args.null_prompt, prompts],
                                cfg_guidance=args.cfg_guidance, target_size=(1024, 1024), callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
+                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver), **_region_kwargs(args, solver))
     else:                                   # "sd20" is accepted and runs SD1.5, like the reference (quirk Q8)
         from cfgpp_amd.latent_diffusion import get_solver
         solver = (get_lcm_solver("lcm", model="sd15", **kw) if lcm else get_sde_solver(args.method, model="sd15", **kw) if sde
                   else get_solver(args.method, **kw))
         result = solver.sample(prompt=[args.null_prompt, prompts], cfg_guidance=args.cfg_guidance, callback_fn=callback, seeds=seeds,
-                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver))
+                               **_control_kwargs(args, solver), **_ip_fit_embeds(ip_kwargs, solver), **_region_kwargs(args, solver))
 
     for i in range(result.shape[0]):
         name = "generated.png" if result.shape[0] == 1 else f"generated_{i}.png"
         save_image(result[i:i + 1], args.workdir / "result" / name, normalize=True)
     print(f"saved {result.shape[0]} image(s) to {args.workdir / 'result'}")
+
+
+def _region_kwargs(args, solver):
+    """--region X0,Y0,X1,Y1:PROMPT (repeatable) -> sample() kwargs: the region prompts and their rectangle masks at latent size"""
+    if not args.region:
+        return {}
+    from cfgpp_amd.regions import parse_region, rect_mask
+    if args.max_regions < 1 + len(args.region):
+        raise SystemExit(f"--region given {len(args.region)} times: needs --max_regions {1 + len(args.region)} (the prompt is region 0; up to 4)")
+    parsed = [parse_region(r) for r in args.region]
+    return dict(region_prompts=[p for _, p in parsed], region_masks=[rect_mask(*rect, solver.latent_hw) for rect, _ in parsed])
 
 
 def _ip_kwargs(args, kw):
