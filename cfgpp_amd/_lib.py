@@ -134,6 +134,11 @@ DPMPP_SDE_PROTOTYPES = {
     "cfgpp_step_sde_stage": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, C.POINTER(C.c_float), _I, _I, _P, _P, _S, _I, _L, _U, _U, _P]),
 }
 
+# the img2img / hires-fix extension header (include/cfgpp_img2img.h): the fused resample + forward-noise start
+IMG2IMG_PROTOTYPES = {
+    "cfgpp_img2img_start": (_I, [_P, _P, _P, _S, _F, _F, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+}
+
 # the MultiDiffusion panorama extension header (include/cfgpp_panorama.h): the window gather and the fused view step
 class PanoViewsC(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "C", "Hp", "Wp", "h", "w", "stride", "circular", "chunk_views")]
@@ -272,7 +277,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(REGIONS_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(REGIONS_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(IMG2IMG_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -23,6 +23,7 @@ SOURCES = [
     ("sde_kernels.hip", ["-ffp-contract=off"]),      # the DPM++ 2M / 3M SDE step (include/cfgpp_sde.h): the same contract, the same Philox
     ("dpmpp_sde_kernels.hip", ["-ffp-contract=off"]),    # the DPM++ SDE stage (include/cfgpp_dpmpp_sde.h): the same contract, the same Philox
     ("pano_kernels.hip", ["-ffp-contract=off"]),     # the MultiDiffusion view step (include/cfgpp_panorama.h): the same contract
+    ("img2img_kernels.hip", ["-ffp-contract=off"]),  # the img2img / hires-fix start (include/cfgpp_img2img.h): the same contract, the same Philox
     ("norm_kernels.hip", []),
     ("small_kernels.hip", []),
     ("igemm_kernel.hip", []),

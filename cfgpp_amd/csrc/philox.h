@@ -1,10 +1,11 @@
 // The counter-based normal generator of include/cfgpp_lcm.h, shared by the kernels that draw noise in registers (lcm_kernels.hip,
-// sde_kernels.hip, dpmpp_sde_kernels.hip): ONE definition, so that a draw inside a step kernel is the instruction sequence of cfgpp_philox_normal's fill and
+// sde_kernels.hip, dpmpp_sde_kernels.hip, img2img_kernels.hip): ONE definition, so that a draw inside a step kernel is the instruction sequence of cfgpp_philox_normal's fill and
 // gives the same bits.  Every file that includes this is built with -ffp-contract=off and without fast-math (cfgpp_amd/build.py).
 //
 // Philox4x32-10 keyed by the chain's 64-bit seed, counter (q, 0, draw, stream_id) with q the 4-element group inside the chain's row;
 // the four outputs are two Box-Muller pairs.  stream_id 0: LCM renoise, 1: ancestral noise, 2: the 2M / 3M SDE solvers' step noise,
-// 3: the path increments of the two-stage DPM++ SDE solver (two draws per step, both read by both stages).
+// 3: the path increments of the two-stage DPM++ SDE solver (two draws per step, both read by both stages), 4: the forward noise of an
+// img2img / hires-fix start (include/cfgpp_img2img.h; draw 0).
 #pragma once
 #include "common.h"
 

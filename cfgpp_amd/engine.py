@@ -354,6 +354,53 @@ def step_sde_stage(x: torch.Tensor, base: torch.Tensor, out: torch.Tensor, den_o
 
 
 # ----------------------------------------------------------------------------
+# img2img / latent hires fix (include/cfgpp_img2img.h)
+# ----------------------------------------------------------------------------
+RESAMPLE_MODES = {"identity": 0, "nearest-exact": 1, "bilinear": 2, "bicubic": 3}
+START_NOISE_STREAM = 4      # stream id of the start's forward noise (draw 0); 0 .. 3: LCM renoise, ancestral, 2M / 3M SDE, DPM++ SDE
+
+
+def img2img_start(x: torch.Tensor, src: Optional[torch.Tensor], a: float, s: float, mode="identity", noise: Optional[torch.Tensor] = None,
+                  seeds=None):
+    """``x = a * resample(src) + s * n`` in one launch (cfgpp_img2img_start): ``x`` [B, C, h, w] fp32 or fp16 is written; ``src``
+    [1 or B, C, h0, w0] fp32 or fp16 (not read, and may be None, when ``a == 0``); ``mode``: a key of ``RESAMPLE_MODES`` or its number;
+    the normals are ``noise`` (fp32, x's shape) or, with None, drawn in the kernel from ``seeds`` (one per chain); ``s == 0`` needs
+    neither."""
+    lib = _lib.load()
+    _require_cuda(x, "x")
+    if x.dim() != 4 or x.dtype not in (torch.float16, torch.float32):
+        raise CfgppError("img2img_start: x must be fp32 or fp16 [B, C, h, w]")
+    B, C_, h, w = (int(v) for v in x.shape)
+    a, s = float(a), float(s)
+    mode = RESAMPLE_MODES[mode] if isinstance(mode, str) else int(mode)
+    rows, h0, w0, src_half = 1, h, w, 0
+    if a != 0.0:
+        if src is None:
+            raise CfgppError("img2img_start: a != 0 needs src")
+        _require_cuda(src, "src")
+        if src.dim() != 4 or src.dtype not in (torch.float16, torch.float32) or int(src.shape[1]) != C_ or int(src.shape[0]) not in (1, B):
+            raise CfgppError(f"img2img_start: src must be fp32 or fp16 [1 or {B}, {C_}, h0, w0], got {src.dtype} {list(src.shape)}")
+        rows, h0, w0, src_half = int(src.shape[0]), int(src.shape[2]), int(src.shape[3]), int(src.dtype == torch.float16)
+    else:                       # the source plays no part: the identity geometry of x
+        src, mode = None, 0
+    sd = None
+    if s != 0.0:
+        if noise is not None:
+            _require_cuda(noise, "noise")
+            if noise.dtype != torch.float32 or tuple(noise.shape) != tuple(x.shape):
+                raise CfgppError("img2img_start: noise must be fp32 of x's shape")
+        elif seeds is None:
+            raise CfgppError("img2img_start: s != 0 needs noise or seeds")
+        else:
+            sd = _seed_array(seeds, B, "img2img_start")
+    else:
+        noise = None
+    check(lib.cfgpp_img2img_start(x.data_ptr(), _ptr(src), _ptr(noise), sd, a, s, B, rows, C_, h0, w0, h, w, mode,
+                                  int(x.dtype == torch.float16), src_half, _stream_ptr(x)), "cfgpp_img2img_start")
+    return x
+
+
+# ----------------------------------------------------------------------------
 # MultiDiffusion panoramas (include/cfgpp_panorama.h)
 # ----------------------------------------------------------------------------
 def _pano_views_c(g, B: int, C_: int, name: str, z_pano: torch.Tensor, z_views: torch.Tensor):

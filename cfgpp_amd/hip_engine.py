@@ -309,6 +309,8 @@ class HipEngine:
     step_sde = staticmethod(E.step_sde)
     # DPM++ SDE (include/cfgpp_dpmpp_sde.h)
     step_sde_stage = staticmethod(E.step_sde_stage)
+    # img2img / latent hires fix (include/cfgpp_img2img.h)
+    img2img_start = staticmethod(E.img2img_start)
     # MultiDiffusion panoramas (include/cfgpp_panorama.h)
     gather_views = staticmethod(E.gather_views)
     step_ddim_views = staticmethod(E.step_ddim_views)
