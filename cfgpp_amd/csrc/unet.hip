@@ -366,7 +366,9 @@ static cfgpp_unet* unet_new(const cfgpp_unet_config* cfg, int device_id, const i
         return nullptr;
     }
     if ((cfg->sample_h % (1 << (cfg->num_levels - 1))) || (cfg->sample_w % (1 << (cfg->num_levels - 1)))) {
-        cfgpp_set_error("unet_create: sample size must be divisible by 2^(levels-1)"); return nullptr;
+        cfgpp_set_error("unet_create: sample size %d x %d must be divisible by 2^(levels-1) = %d", cfg->sample_h, cfg->sample_w,
+                        1 << (cfg->num_levels - 1));
+        return nullptr;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device_id) {

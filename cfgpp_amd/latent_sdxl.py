@@ -190,8 +190,11 @@ class SDXL(StableDiffusion):
         return z
 
     def _latent_size(self, shape):
+        """the latent of ``shape`` = target_size = (height, width), the order of the time_ids and of diffusers.  (The reference forms
+        (shape[1] // 8, shape[0] // 8), latent_sdxl.py:439: the same for the square sizes it runs, and for any other size a latent
+        transposed against its own time_ids - which the engine, built for ``latent_hw`` = (H, W), refuses.)"""
         B = getattr(self, "_batch", 1)
-        return (B, 4, shape[1] // self.vae_scale_factor, shape[0] // self.vae_scale_factor)
+        return (B, 4, shape[0] // self.vae_scale_factor, shape[1] // self.vae_scale_factor)
 
     def _split_cond_for_inversion(self, cfg_guidance, add_cond_kwargs):
         # lambda in {0,1}: add_cond_kwargs is reduced IN PLACE to its last row (latent_sdxl.py:302-305)

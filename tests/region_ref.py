@@ -1,7 +1,7 @@
 """The fp32 CPU oracle of regional prompts: oracle.unet_ref.UNetRef with, for attn2 only, the per-pixel selection - the query at
 pixel p of region r attends to the context tokens [77 r, 77 r + 77) alone.  The map of a level is derived from the token count N of
-the call: side = sqrt(N), the nearest downsample id_l[y, x] = id_0[y * f, x * f] with f = H0 / side (F.interpolate(mode="nearest")
-for these integer factors).  Everything else is the parent's.
+the call: f = sqrt(H0 W0 / N), the level is H0 / f x W0 / f (the latent need not be square), the nearest downsample
+id_l[y, x] = id_0[y * f, x * f] (F.interpolate(mode="nearest") for these integer factors).  Everything else is the parent's.
 
 ``fault`` makes the three mistakes an engine can make with the map, for the loudness check of tests/test_gpu_regions_net.py:
   swapped         regions 0 and 1 exchanged
@@ -38,18 +38,20 @@ class RegionUNetRef(UNetRef):
         self.n_regions, self.fault = int(n_regions), fault
         return self
 
-    def level_map(self, B, N):
+    def level_ids(self, N):
+        """the map of the level with N tokens, [map rows, H0 / f, W0 / f]"""
         ids = self.ids
-        H0 = ids.shape[-1]
-        side = int(math.isqrt(N))
-        assert side * side == N and H0 % side == 0
-        f = H0 // side
+        H0, W0 = ids.shape[-2:]
+        f = int(math.isqrt(H0 * W0 // N))
+        assert f >= 1 and H0 % f == 0 and W0 % f == 0 and (H0 // f) * (W0 // f) == N
         if self.fault == "swapped":
             ids = torch.where(ids == 0, 1, torch.where(ids == 1, 0, ids))
         if self.fault == "shifted":
             ids = torch.roll(ids, 1, dims=-1)
-        m = ids[:, :side, :side] if self.fault == "no_downsample" else ids[:, ::f, ::f]
-        return m.reshape(-1, N).expand(B, N)
+        return ids[:, :H0 // f, :W0 // f] if self.fault == "no_downsample" else ids[:, ::f, ::f]
+
+    def level_map(self, B, N):
+        return self.level_ids(N).reshape(-1, N).expand(B, N)
 
     def _attn(self, p, x, ctx, heads):
         if self.ids is None or not p.endswith(".attn2"):
@@ -95,10 +97,12 @@ def region_context(rows, n_regions, dim, seed=81):
 
 
 def region_ids(kind, n_regions, rows=1, hw=HW):
-    """left/right stripes or a checkerboard of n_regions ids -> int64 [rows, hw, hw]; rows > 1: row b's map is rolled by 3 b pixels"""
-    y, x = torch.meshgrid(torch.arange(hw), torch.arange(hw), indexing="ij")
+    """left/right stripes or a checkerboard of n_regions ids -> int64 [rows, h, w] (``hw``: one side, or a pair (h, w)); rows > 1: row
+    b's map is rolled by 3 b pixels"""
+    h, w = (hw, hw) if isinstance(hw, int) else hw
+    y, x = torch.meshgrid(torch.arange(h), torch.arange(w), indexing="ij")
     if kind == "stripes":
-        m = (x * n_regions // hw).clamp(max=n_regions - 1)
+        m = (x * n_regions // w).clamp(max=n_regions - 1)
     elif kind == "checker":
         m = (x + y) % n_regions
     else:

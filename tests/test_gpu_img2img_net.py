@@ -48,10 +48,10 @@ def _cfg(model):
     return TINY_SD if model == "sd15" else TINY_XL
 
 
-def _solver(model, name, **kw):
+def _solver(model, name, hw=HW, **kw):
     from cfgpp_amd.img2img import get_img2img_solver
     return get_img2img_solver(name, model=model, solver_config=types.SimpleNamespace(num_sampling=5), unet_config=_cfg(model), max_batch=2,
-                              latent_hw=HW, scalar_semantics="cuda", **kw)
+                              latent_hw=hw, scalar_semantics="cuda", **kw)
 
 
 def _embeds(s, model):
@@ -70,10 +70,10 @@ def _sample(s, model, pe, seeds, lam, **kw):
 class OracleMock(Img2ImgMockEngine):
     """the mock engine whose UNet is the oracle"""
 
-    def __init__(self, cfg, sd):
+    def __init__(self, cfg, sd, hw=HW):
         from oracle.unet_ref import UNetRef
         self.net = UNetRef(cfg, sd)
-        super().__init__(self._unet, HW)
+        super().__init__(self._unet, hw)
 
     def _unet(self, z, t, ehs, te, ti):
         ack = None if te is None else {"text_embeds": te.float(), "time_ids": ti.float()}
@@ -102,11 +102,11 @@ class MeanVAE:
         return self.v.decode(z)
 
 
-def _source(case):
+def _source(case, hw=HW, small=SMALL):
     g = torch.Generator().manual_seed(31)
     if case.endswith("src_img"):
-        return dict(src_img=torch.rand((2, 3, 8 * HW[0], 8 * HW[1]), generator=g) * 2 - 1)
-    return dict(src_latents=torch.randn((2, 4) + SMALL, generator=g), upscale="bilinear")
+        return dict(src_img=torch.rand((2, 3, 8 * hw[0], 8 * hw[1]), generator=g) * 2 - 1)
+    return dict(src_latents=torch.randn((2, 4) + small, generator=g), upscale="bilinear")
 
 
 @pytest.mark.parametrize("case", list(CASES))
