@@ -102,6 +102,12 @@ REGIONS_PROTOTYPES = {
     "cfgpp_unet_set_regions": (_I, [_P, _P, _I, _I]),
 }
 
+# the soft regional-prompt extension header (include/cfgpp_regions_soft.h)
+REGIONS_SOFT_PROTOTYPES = {
+    "cfgpp_unet_enable_region_weights": (_I, [_P]),
+    "cfgpp_unet_set_region_weights": (_I, [_P, _P, _I, _I]),
+}
+
 # the FreeU extension header (include/cfgpp_freeu.h)
 FREEU_PROTOTYPES = {
     "cfgpp_unet_set_freeu": (_I, [_P, _F, _F, _F, _F, _I]),
@@ -183,6 +189,7 @@ DEBUG_PROTOTYPES = {
     "cfgpp_op_attention_clear_slots": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_ip": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P]),
     "cfgpp_op_attention_region": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+    "cfgpp_op_attention_region_soft": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P]),
     "cfgpp_op_perceiver_attention": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_op_attention_vit": (_I, [_P, _P, _I, _I, _I, _I, _P]),
     "cfgpp_vit_attention_last_launch": (None, [C.POINTER(C.c_int)]),
@@ -277,7 +284,7 @@ def load():
         lib = C.CDLL(LIB_PATH)
     except OSError as e:  # pragma: no cover
         raise CfgppError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(REGIONS_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(IMG2IMG_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(IP_ADAPTER_PROTOTYPES.items()) + list(IP_PLUS_PROTOTYPES.items()) + list(LONG_PROMPT_PROTOTYPES.items()) + list(REGIONS_PROTOTYPES.items()) + list(REGIONS_SOFT_PROTOTYPES.items()) + list(FREEU_PROTOTYPES.items()) + list(VPRED_PROTOTYPES.items()) + list(LCM_PROTOTYPES.items()) + list(SDE_PROTOTYPES.items()) + list(DPMPP_SDE_PROTOTYPES.items()) + list(IMG2IMG_PROTOTYPES.items()) + list(PANORAMA_PROTOTYPES.items()) + list(VISION_PROTOTYPES.items()) + list(DEBUG_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

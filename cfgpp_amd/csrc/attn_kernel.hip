@@ -1183,6 +1183,229 @@ attn_region_rows_kernel(const AttnArgs a, int dp, const unsigned char* __restric
     }
 }
 
+// ---- soft regional cross-attention, every padded head dim: R = 2 .. 4 prompts of 77 tokens BLENDED per query ----------------------
+//     o = fp16( sum_r  w_r(q) / l_r  *  O_r ),    O_r = P_r V_r,  P_r = fp16(2^(s - m_r)) over keys [77 r, 77 r + 77) alone
+// w is fp32 [map_rows][n_regions][q_tok_pad] (pads 0).  Every region's softmax is COMPLETE (77 keys, its own maximum, its own
+// denominator), so nothing is re-referenced across regions and a lane carries no "own key met" state.  The frame is attn_kernel's
+// (S^T layout: a lane owns a query; K / V^T tiles through padded LDS rows; P from the accumulator registers into the PV MFMA): keys
+// [77 r, 77 r + 77) lie inside the two 64-key tiles r and r + 1 (77 r >> 6 == r and (77 r + 76) >> 6 == r + 1 for r = 0 .. 3), which
+// are staged together (at dp = 160: 2 x 44.5 KB; the K / V^T of four regions would not fit, so regions are STREAMED through the one
+// stage).  All 128 scores of the two tiles stay in registers (keys outside the region -inf; a 32-key sub-tile without a key of the
+// region is neither multiplied nor exponentiated: r = 0, 1, 3 have three live sub-tiles, r = 2 four), the maximum is exact, the
+// denominator is the ones row of V^T met by the rounded P (d % 32 != 0) or the fp32 sum of the ROUNDED P.
+// Region skipping is a WORKGROUP vote: the tile loads sit behind __syncthreads, so the decision is taken from one LDS word per wave
+// that every wave reads after a barrier - all four waves see the same four words, take the same branches and meet the same number of
+// barriers.  A region in which no query of the workgroup's 128 has w != 0 is not loaded.  Inside an evaluated region a lane with
+// w_r == 0 keeps its total as it is (a select, not a multiply by 0: the region's keys and values may hold junk that overflows).
+// The vote words are the first 16 bytes of the DYNAMIC LDS (a static __shared__ would shift the 16-byte alignment of the tiles).
+template <int D16, int DT, bool ONES>
+__global__ void __launch_bounds__(256)
+attn_region_soft_kernel(const AttnArgs a, const float* __restrict__ w, int w_bstride /* 0 (one map for all rows) or n_regions * q_tok_pad */,
+                        int n_regions) {
+    constexpr int DP = DT * 32;
+    constexpr int KPITCH = DP * 2 + 16;          // bytes per K row in LDS
+    constexpr int VPITCH = 64 * 2 + 16;          // bytes per V^T row in LDS (64 keys)
+    constexpr int CH = (64 * DP / 8) / 256;      // 16-B chunks per thread per tile (K and V each)
+    constexpr int STAGE = 64 * KPITCH + DP * VPITCH;
+    static_assert((64 * DP / 8) % 256 == 0 && STAGE % 16 == 0, "tile/loader mismatch");
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // votes (16 B) | tile r (K | V^T) | tile r + 1 (K | V^T)
+    int* vote = reinterpret_cast<int*>(smem);
+    char* tiles = smem + 16;
+
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int l31 = lane & 31, hi = lane >> 5;
+    int qb, bh;
+    attn_block_map(a.nqb, qb, bh);
+    const int q0 = qb * 128 + wid * 32;
+    const int b = bh / a.heads, head = bh - b * a.heads;
+    const half_t* Qb = a.q + (long)bh * a.q_tok_pad * DP;
+    const half_t* Kb = a.k + (long)bh * a.k_tok_pad * DP;
+    const half_t* Vb = a.vt + (long)bh * DP * a.k_tok_pad;
+
+    // the lane's query's weights (q0 + l31 < nqb * 128 <= q_tok_pad: inside the row), and the workgroup's vote
+    const float* wq = w + (long)b * w_bstride + q0 + l31;
+    float wv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) wv[r] = r < n_regions ? wq[(long)r * a.q_tok_pad] : 0.f;
+    int mine = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mine |= __any(wv[r] != 0.f) ? (1 << r) : 0;
+    if (lane == 0) vote[wid] = mine;
+    __syncthreads();
+    const int live = __builtin_amdgcn_readfirstlane(vote[0] | vote[1] | vote[2] | vote[3]);     // the same in every wave
+
+    half8_t qf[D16];
+#pragma unroll
+    for (int ks = 0; ks < D16; ++ks) {
+        const half8_t raw = *reinterpret_cast<const half8_t*>(Qb + (long)(q0 + l31) * DP + ks * 16 + hi * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qf[ks][j] = (half_t)((float)raw[j] * a.scale_log2e);
+    }
+    f32x16 otot[DT];
+#pragma unroll
+    for (int i = 0; i < DT; ++i)
+#pragma unroll
+        for (int rr = 0; rr < 16; ++rr) otot[i][rr] = 0.f;
+
+#pragma unroll 1
+    for (int r = 0; r < 4; ++r) {
+        if (!((live >> r) & 1)) continue;        // WORKGROUP-uniform (see above): every wave skips, or none does
+        const float wr = r == 0 ? wv[0] : r == 1 ? wv[1] : r == 2 ? wv[2] : wv[3];
+        __syncthreads();                         // every wave is done with the previous region's tiles
+        {
+            half8_t rk[2][CH], rv[2][CH];
+#pragma unroll
+            for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    const int c = tid + j * 256;
+                    const int kr = c / (DP / 8), kc = c - kr * (DP / 8);
+                    rk[tl][j] = *reinterpret_cast<const half8_t*>(Kb + (long)((r + tl) * 64 + kr) * DP + kc * 8);
+                    const int vr = c >> 3, vc = c & 7;
+                    rv[tl][j] = *reinterpret_cast<const half8_t*>(Vb + (long)vr * a.k_tok_pad + (r + tl) * 64 + vc * 8);
+                }
+#pragma unroll
+            for (int tl = 0; tl < 2; ++tl) {
+                char* Ks = tiles + tl * STAGE;
+                char* Vs = Ks + 64 * KPITCH;
+#pragma unroll
+                for (int j = 0; j < CH; ++j) {
+                    const int c = tid + j * 256;
+                    const int kr = c / (DP / 8), kc = c - kr * (DP / 8);
+                    *reinterpret_cast<half8_t*>(Ks + kr * KPITCH + kc * 16) = rk[tl][j];
+                    const int vr = c >> 3, vc = c & 7;
+                    *reinterpret_cast<half8_t*>(Vs + vr * VPITCH + vc * 16) = rv[tl][j];
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- S^T = K Q^T for the region's 32-key sub-tiles (log2 domain), keys outside [77 r, 77 r + 77) masked ----
+        // register rr of sub-tile st holds key r * 64 + st * 32 + (rr & 3) + 8 (rr >> 2) + 4 hi
+        const int own0 = 77 * r;
+        f32x16 s[4];
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const int lo = r * 64 + st * 32;
+            if (lo < own0 + 77 && lo + 32 > own0) {              // (workgroup-uniform) the sub-tile holds a key of the region
+                const char* Ks = tiles + (st >> 1) * STAGE;
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) s[st][rr] = 0.f;
+#pragma unroll
+                for (int ks = 0; ks < D16; ++ks) {
+                    const half8_t kf = *reinterpret_cast<const half8_t*>(Ks + ((st & 1) * 32 + l31) * KPITCH + (ks * 16 + hi * 8) * 2);
+                    s[st] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], s[st], 0, 0, 0);
+                }
+                const int rel0 = lo + 4 * hi - own0;
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr)
+                    s[st][rr] = (unsigned)(rel0 + ((rr & 3) + 8 * (rr >> 2))) < 77u ? s[st][rr] : -INFINITY;
+            } else {
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) s[st][rr] = -INFINITY;
+            }
+        }
+        // ---- the region's complete softmax: exact maximum over its 77 keys, P rounded to fp16 ----
+        float mx = -INFINITY;
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const int lo = r * 64 + st * 32;
+            if (lo < own0 + 77 && lo + 32 > own0) {              // (workgroup-uniform) a dead sub-tile enters neither the maximum ..
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) mx = fmaxf(mx, s[st][rr]);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float psum = 0.f;
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const int lo = r * 64 + st * 32;
+            if (lo < own0 + 77 && lo + 32 > own0) {              // .. nor the exponentials (its P is never read: the PV loop skips it too)
+#pragma unroll
+                for (int rr = 0; rr < 16; ++rr) {
+                    const float pv = __builtin_amdgcn_exp2f(s[st][rr] - mx);
+                    s[st][rr] = pv;
+                    if constexpr (!ONES) psum += (float)(half_t)pv;
+                }
+            }
+        }
+        // ---- O_r^T = V_r^T P^T ----
+        f32x16 oacc[DT];
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) oacc[i][rr] = 0.f;
+#pragma unroll
+        for (int st = 0; st < 4; ++st) {
+            const int lo = r * 64 + st * 32;
+            if (lo < own0 + 77 && lo + 32 > own0) {
+                const char* Vs = tiles + (st >> 1) * STAGE + 64 * KPITCH;
+#pragma unroll
+                for (int tt = 0; tt < 2; ++tt) {
+                    half8_t pf;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pf[j] = (half_t)s[st][8 * tt + j];
+                    const int kpos0 = (st & 1) * 32 + 16 * tt + 8 * hi;
+#pragma unroll
+                    for (int i = 0; i < DT; ++i) {
+                        const half8_t vf = *reinterpret_cast<const half8_t*>(Vs + (i * 32 + l31) * VPITCH + kpos0 * 2);
+                        oacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf, oacc[i], 0, 0, 0);
+                    }
+                }
+            }
+        }
+        // ---- total += (w_r / l_r) O_r for the lanes whose query has w_r != 0 ----
+        float l_r;
+        if constexpr (ONES) {
+            const int dr = a.d & 31;                                   // multiple of 8 by contract
+            float lv = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) if (dr == 8 * g) lv = oacc[DT - 1][4 * g];
+            l_r = __shfl(lv, l31);
+        } else {
+            l_r = psum + __shfl_xor(psum, 32);
+        }
+        const bool on = wr != 0.f;
+        const float coef = on ? wr / l_r : 0.f;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int rr = 0; rr < 16; ++rr) otot[i][rr] = on ? fmaf(coef, oacc[i][rr], otot[i][rr]) : otot[i][rr];
+    }
+
+    // ---- store token-major: one rounding ----
+    const int q = q0 + l31;
+    if (q < a.nq) {
+        half_t* orow = a.o + ((long)b * a.nq + q) * a.o_ld + head * a.d;
+#pragma unroll
+        for (int i = 0; i < DT; ++i)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int dd = i * 32 + 8 * g + 4 * hi;
+                if (dd < a.d) {
+                    half4_t o;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = (half_t)otot[i][4 * g + k];
+                    *reinterpret_cast<half4_t*>(orow + dd) = o;
+                }
+            }
+    }
+}
+
+template <int D16, int DT, bool ONES>
+int launch_attn_region_soft(const AttnArgs& a, dim3 grid, hipStream_t s, const float* w, int w_bstride, int n_regions) {
+    constexpr int DP = DT * 32;
+    constexpr int smem = 16 + 2 * (64 * (DP * 2 + 16) + DP * (64 * 2 + 16));
+    static bool attr_set = false;
+    auto kern = attn_region_soft_kernel<D16, DT, ONES>;
+    if (!attr_set) {
+        CFGPP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(256), smem, s, a, w, w_bstride, n_regions);
+    return 0;
+}
+
 template <int D16, bool ONES, int NST, int WPE = 3>
 int launch_attn64(const AttnArgs& a, dim3 grid, hipStream_t s) {
     constexpr int smem = NST * 2 * 64 * 128;
@@ -1569,6 +1792,49 @@ int cfgpp_op_attention_region(const void* q, const void* k, const void* vt, void
     hipLaunchKernelGGL(attn_region_rows_kernel, dim3(cdiv(nq, 256), BH), dim3(256), 0, s, a, dt * 32, idp, ids_bstride, n_regions);
     CFGPP_HIP_CHECK(hipGetLastError());
     attn_note(8, d16, ones, 0);
+    return 0;
+}
+
+// Soft regional cross-attention: buffers as for cfgpp_op_attention_region; w is a DEVICE fp32 [map_rows][n_regions][q_tok_pad]
+// (map_rows = 1 or B, pads 0) and query p of row b answers with fp16( sum_r w[b][r][p] * softmax(q K_r) V_r ), every region's softmax
+// complete over its own 77 keys; a term with w == 0 is not evaluated.  attn_region_soft_kernel for every head dim cfgpp_op_attention
+// has an instance for (record: kernel 9, xqb 0); the other head dims are refused by name.  The A/B switches do not reach it.
+int cfgpp_op_attention_region_soft(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int n_regions,
+                                   const void* w, int map_rows, int q_tok_pad, int k_tok_pad, void* stream) {
+    attn_note(0, 0, 0, 0);
+    CFGPP_REQUIRE(q && k && vt && o, "attention_region_soft: null pointer");
+    CFGPP_REQUIRE(w, "attention_region_soft: null weights (a device fp32 [map_rows][n_regions][q_tok_pad] map)");
+    CFGPP_REQUIRE(B > 0 && heads > 0 && nq > 0, "attention_region_soft: B=%d heads=%d nq=%d", B, heads, nq);
+    CFGPP_REQUIRE(n_regions >= 2 && n_regions <= 4, "attention_region_soft: n_regions=%d (2 .. 4 regions of 77 keys)", n_regions);
+    CFGPP_REQUIRE(map_rows == 1 || map_rows == B, "attention_region_soft: map_rows=%d (1 or B=%d)", map_rows, B);
+    CFGPP_REQUIRE(d > 0 && d <= 160 && d % 8 == 0, "attention_region_soft: head dim %d unsupported (multiple of 8, <= 160)", d);
+    CFGPP_REQUIRE(q_tok_pad % 128 == 0 && q_tok_pad >= nq, "attention_region_soft: q_tok_pad=%d (nq=%d) must be a multiple of 128", q_tok_pad, nq);
+    // region r is read as the two 64-key tiles r and r + 1: 64 (n_regions + 1) == round_up(77 n_regions, 64) slots for 2 .. 4 regions
+    const int nk = 77 * n_regions, need = 64 * (n_regions + 1);
+    CFGPP_REQUIRE(k_tok_pad % 64 == 0 && k_tok_pad >= need, "attention_region_soft: k_tok_pad=%d must be a multiple of 64 and >= %d (n_regions=%d: %d keys)",
+                  k_tok_pad, need, n_regions, nk);
+    AttnArgs a;
+    a.q = (const half_t*)q; a.k = (const half_t*)k; a.vt = (const half_t*)vt; a.o = (half_t*)o;
+    a.heads = heads; a.d = d; a.nq = nq; a.nk_valid = nk; a.q_tok_pad = q_tok_pad; a.k_tok_pad = k_tok_pad;
+    a.o_ld = heads * d;
+    a.scale_log2e = (1.0f / sqrtf((float)d)) * 1.4426950408889634f;
+    a.nqb = cdiv(nq, 128);
+    a.stagger = 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int d16 = (d + 15) / 16, dt = (d + 31) / 32;
+    const bool ones = (d % 32) != 0;
+    const dim3 grid(a.nqb * B * heads);
+    const float* wp = (const float*)w;
+    const int w_bstride = map_rows == 1 ? 0 : n_regions * q_tok_pad;
+#define SOFT_CASE(D16_, DT_, ONES_) \
+    if (d16 == D16_ && dt == DT_ && ones == ONES_) { if (launch_attn_region_soft<D16_, DT_, ONES_>(a, grid, s, wp, w_bstride, n_regions)) return -1; } else
+    SOFT_CASE(1, 1, true) SOFT_CASE(2, 1, true) SOFT_CASE(2, 1, false) SOFT_CASE(3, 2, true) SOFT_CASE(4, 2, true) SOFT_CASE(4, 2, false)
+    SOFT_CASE(5, 3, true) SOFT_CASE(6, 3, true) SOFT_CASE(6, 3, false) SOFT_CASE(8, 4, true) SOFT_CASE(8, 4, false)
+    SOFT_CASE(10, 5, true) SOFT_CASE(10, 5, false)
+    { cfgpp_set_error("attention_region_soft: no kernel instance for head dim %d", d); return -2; }
+#undef SOFT_CASE
+    CFGPP_HIP_CHECK(hipGetLastError());
+    attn_note(9, d16, ones, 0);
     return 0;
 }
 

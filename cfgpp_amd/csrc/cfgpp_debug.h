@@ -87,7 +87,7 @@ int cfgpp_op_attention_cross(const void* q, const void* k, const void* vt, void*
 void cfgpp_attention_set_cross_long(int mode);
 /* test hook: what the last cfgpp_op_attention call dispatched, a host-side record: out4 = {kernel (0 nothing launched: the call
  * was refused, 1 attn_kernel, 2 attn64_kernel, 3 xattn64_kernel, 4 xattn64_kernel IP form, 5 attn_ip_add_kernel, 6 xattn64_long_kernel,
- * 7 xattn64_region_kernel, 8 attn_region_rows_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
+ * 7 xattn64_region_kernel, 8 attn_region_rows_kernel, 9 attn_region_soft_kernel), D16 (16-wide k-steps of QK^T), ONES (1: the denominator comes
  * from the ones row of V^T), xqb (128-query blocks per workgroup of xattn64_kernel, 0 for the flash kernels)} */
 void cfgpp_attention_last_launch(int* out4);
 /* zero key slots [slot0, slot0 + n) of k [BH][tok_pad][dp] and of rows < d of vt [BH][dp][tok_pad] (the ones row stays) */
@@ -111,6 +111,19 @@ int cfgpp_op_attention_ip(const void* q, const void* k, const void* vt, void* o,
  * null ids. */
 int cfgpp_op_attention_region(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int n_regions,
                               const void* ids, int map_rows, int q_tok_pad, int k_tok_pad, void* stream);
+/* Soft regional cross-attention: buffers as for cfgpp_op_attention_region; w is a DEVICE fp32 [map_rows][n_regions][q_tok_pad] with
+ * map_rows = 1 or B and zero pads, and query p of batch row b answers with
+ *   o = fp16( sum_r w[b][r][p] / l_r * O_r ),   O_r = P_r V_r,  P_r = fp16(2^(s - m_r)),  l_r = sum of those fp16 P_r
+ * over the regions r (ascending) with w != 0: every region's softmax is complete over its own keys [77 r, 77 r + 77) - scores from q
+ * pre-scaled by d^-1/2 log2(e) and rounded to fp16, m_r their exact maximum - the sum runs in fp32 and the store is the one fp16
+ * rounding.  A term with w == 0 is not evaluated: the keys and values of such a region, and the slots [77 * n_regions, k_tok_pad),
+ * may hold anything finite.  One-hot weights give the hard partition of cfgpp_op_attention_region.  last_launch kernel 9
+ * (attn_region_soft_kernel: an MFMA instance for every head dim cfgpp_op_attention has one for, regions streamed through LDS two
+ * 64-key tiles at a time, a region no query of the workgroup weighs is skipped by a workgroup-wide vote), xqb 0.  Refused by name,
+ * nothing launched: a head dim without an instance, n_regions outside 2 .. 4, k_tok_pad < 64 (n_regions + 1), map_rows not 1 or B,
+ * null w. */
+int cfgpp_op_attention_region_soft(const void* q, const void* k, const void* vt, void* o, int B, int heads, int d, int nq, int n_regions,
+                                   const void* w, int map_rows, int q_tok_pad, int k_tok_pad, void* stream);
 /* Perceiver attention of the IP-Adapter "plus" Resampler (include/cfgpp_ip_plus.h; csrc/resampler.hip), head dim 64:
  *   o[r][j][h*64 ..] = fp16( softmax_k(q[r][j][h] . k[r][k][h] / 8) v[r][k][h] ),  ONE softmax over the S keys of kv_x followed by the
  *   n_q keys of kv_l.

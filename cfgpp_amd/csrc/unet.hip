@@ -13,6 +13,7 @@
 #include "../../include/cfgpp_ip_plus.h"
 #include "../../include/cfgpp_lcm.h"
 #include "../../include/cfgpp_regions.h"
+#include "../../include/cfgpp_regions_soft.h"
 #include "freeu.h"
 
 struct cfgpp_unet : EngineBase {
@@ -71,6 +72,13 @@ struct cfgpp_unet : EngineBase {
     int regions = 0, region_map_rows = 0;
     unsigned char* d_region_ids[4] = {nullptr, nullptr, nullptr, nullptr};
     int region_h[4] = {0, 0, 0, 0}, region_w[4] = {0, 0, 0, 0};
+    // ---- soft regional prompts (include/cfgpp_regions_soft.h).  soft_enabled (cfgpp_unet_enable_region_weights, before finalize) makes
+    // finalize allocate, next to the id maps, one fp32 weight buffer per level, [max_rows][4][q_pad of the level].  soft_regions = R
+    // = 2 .. 4 (cfgpp_unet_set_region_weights): every cross-attention op calls cfgpp_op_attention_region_soft with its level's weights,
+    // [soft_map_rows][R][q_pad], pads 0.  Soft weights and the hard id map are exclusive: setting one clears the other.
+    bool soft_enabled = false;
+    int soft_regions = 0, soft_map_rows = 0;
+    float* d_region_w[4] = {nullptr, nullptr, nullptr, nullptr};
 
     // time-embedding scratch
     float* d_sin_t = nullptr; float* d_emb_h = nullptr; float* d_emb_t = nullptr; float* d_emb = nullptr;
@@ -149,6 +157,8 @@ struct cfgpp_unet : EngineBase {
             plan_macs[b.plan_idx] = regions ? per_key * 77 : per_key * (ctx_tokens + ip_n_img);      // a regional row attends to its own 77 keys
             plan_desc[b.plan_idx] = on ? desc + " ip=" + std::to_string(n_img) : ctx_tokens != 77 ? desc + " keys=" + std::to_string(ctx_tokens) : desc;
             if (regions) plan_desc[b.plan_idx] += " regions=" + std::to_string(regions);
+            // soft regions: a row may weigh every region, so all 77 R keys are counted (what a fully mixed map runs)
+            if (soft_regions) plan_desc[b.plan_idx] += " soft_regions=" + std::to_string(soft_regions);
         }
     }
     // the profiler's tags of the cross-attention ops follow the token count of the current context
@@ -466,6 +476,10 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                     u->d_region_ids[i] = (unsigned char*)u->dmalloc((size_t)R * round_up((int)tok, 128));
                     CFGPP_REQUIRE(u->d_region_ids[i], "finalize: hipMalloc failed");
                 }
+                if (u->soft_enabled) {          // the region weights of this level (cfgpp_unet_set_region_weights): sized here as well
+                    u->d_region_w[i] = (float*)u->dmalloc((size_t)R * 4 * round_up((int)tok, 128) * sizeof(float));
+                    CFGPP_REQUIRE(u->d_region_w[i], "finalize: hipMalloc failed");
+                }
             }
             if (i != L - 1) { H /= 2; W /= 2; }
         }
@@ -678,6 +692,9 @@ int cfgpp_unet_finalize(cfgpp_unet* u) {
                     if (uu->regions)        // regional prompts: every query attends to the 77 keys of its region, ONE launch, same launch count
                         return cfgpp_op_attention_region(hq, ck, cvt, o, rows, nheads, d, tok, uu->regions, uu->d_region_ids[lvl],
                                                          uu->region_map_rows == 1 ? 1 : rows, q_pad, ck_pad, s);
+                    if (uu->soft_regions)   // soft regional prompts: every query blends the regions' complete softmaxes, ONE launch
+                        return cfgpp_op_attention_region_soft(hq, ck, cvt, o, rows, nheads, d, tok, uu->soft_regions, uu->d_region_w[lvl],
+                                                              uu->soft_map_rows == 1 ? 1 : rows, q_pad, ck_pad, s);
                     if (uu->ip_active)      // IP-Adapter: text + image keys in ONE launch (head dims padded to 64), same launch count
                         return cfgpp_op_attention_ip(hq, ck, cvt, o, rows, nheads, d, tok, uu->ctx_tokens, uu->ip_n_img, uu->ip_scale, q_pad,
                                                      ck_pad, s);
@@ -932,12 +949,92 @@ int cfgpp_unet_set_regions(cfgpp_unet* u, const unsigned char* ids_host, int map
         CFGPP_HIP_CHECK(hipMemcpy(u->d_region_ids[l], lvl_map.data(), lvl_map.size(), hipMemcpyHostToDevice));
     }
     u->regions = n_regions; u->region_map_rows = map_rows;
+    u->soft_regions = 0; u->soft_map_rows = 0;                 // exclusive with the soft weights (include/cfgpp_regions_soft.h)
+    u->retag_cross();
+    return 0;
+}
+
+// Soft regional prompts (include/cfgpp_regions_soft.h)
+int cfgpp_unet_enable_region_weights(cfgpp_unet* u) {
+    CFGPP_REQUIRE(u, "enable_region_weights: null engine");
+    CFGPP_REQUIRE(!u->finalized, "enable_region_weights: after cfgpp_unet_finalize (the per-level weight buffers are allocated there)");
+    CFGPP_REQUIRE(u->max_tokens > 77, "enable_region_weights: max_tokens=%d (regions need max_tokens > 77: cfgpp_unet_set_max_tokens first)", u->max_tokens);
+    u->soft_enabled = true;
+    return 0;
+}
+
+// The level weights are nearest downsamples of the level-0 weights, w_l[r][y][x] = w_0[r][y << l][x << l], made on the host and copied
+// into the buffers finalize sized.
+int cfgpp_unet_set_region_weights(cfgpp_unet* u, const float* w_host, int map_rows, int n_regions) {
+    CFGPP_REQUIRE(u && u->finalized, "set_region_weights: the engine is not finalized");
+    if (!w_host && map_rows == 0 && n_regions == 0) {          // off
+        if (u->soft_regions) { u->soft_regions = 0; u->soft_map_rows = 0; u->retag_cross(); }
+        return 0;
+    }
+    CFGPP_REQUIRE(!u->control, "set_region_weights: a ControlNet-mode engine takes no regional prompts (regions with ControlNet are not built)");
+    CFGPP_REQUIRE(u->ip_kind == cfgpp_unet::IP_NONE && !u->ip_active, "set_region_weights: an IP-Adapter is loaded (regions with an IP-Adapter are not "
+                  "built: its image slots sit at key 96 of the text buffers)");
+    CFGPP_REQUIRE(u->soft_enabled, "set_region_weights: the engine was not enabled for region weights (cfgpp_unet_enable_region_weights before finalize)");
+    CFGPP_REQUIRE(n_regions >= 2 && n_regions <= 4, "set_region_weights: n_regions=%d (2 .. 4; (NULL, 0, 0) turns the weights off)", n_regions);
+    CFGPP_REQUIRE(w_host, "set_region_weights: null weights");
+    CFGPP_REQUIRE(u->max_tokens >= 77 * n_regions, "set_region_weights: n_regions=%d needs max_tokens >= %d, the engine was built with max_tokens=%d "
+                  "(cfgpp_unet_set_max_tokens before finalize)", n_regions, 77 * n_regions, u->max_tokens);
+    CFGPP_REQUIRE(map_rows == 1 || (map_rows >= 1 && map_rows <= u->cfg.max_rows && (!u->ctx_set || map_rows == u->ctx_rows)),
+                  "set_region_weights: map_rows=%d (1, or the context's row count %d)", map_rows, u->ctx_set ? u->ctx_rows : u->cfg.max_rows);
+    const int H0 = u->cfg.sample_h, W0 = u->cfg.sample_w;
+    const long HW = (long)H0 * W0;
+    for (long r = 0; r < map_rows; ++r)
+        for (long p = 0; p < HW; ++p) {
+            float sum = 0.f;
+            for (int g = 0; g < n_regions; ++g) {
+                const float v = w_host[(r * n_regions + g) * HW + p];
+                if (!(v >= 0.f) || !std::isfinite(v)) {
+                    cfgpp_set_error("set_region_weights: weight %g at row %ld, region %d, pixel (%ld, %ld) (weights are finite and >= 0)", (double)v, r, g,
+                                    p / W0, p % W0);
+                    return -2;
+                }
+                sum += v;
+            }
+            if (!(std::fabs(sum - 1.f) <= 1e-4f)) {
+                cfgpp_set_error("set_region_weights: the weights at row %ld, pixel (%ld, %ld) sum to %.7g (1 +- 1e-4)", r, p / W0, p % W0, (double)sum);
+                return -2;
+            }
+        }
+    CFGPP_HIP_CHECK(hipSetDevice(u->device));
+    CFGPP_HIP_CHECK(hipDeviceSynchronize());                   // no forward in flight reads the weights that are rewritten below
+    std::vector<float> lvl_w;
+    for (int l = 0; l < u->cfg.num_levels; ++l) {
+        if (!u->d_region_w[l]) continue;
+        const int h = u->region_h[l], w = u->region_w[l], q_pad = round_up(h * w, 128);
+        const int fy = H0 / h, fx = W0 / w;
+        lvl_w.assign((size_t)map_rows * n_regions * q_pad, 0.f);
+        for (int r = 0; r < map_rows; ++r)
+            for (int g = 0; g < n_regions; ++g)
+                for (int y = 0; y < h; ++y)
+                    for (int x = 0; x < w; ++x)
+                        lvl_w[((size_t)r * n_regions + g) * q_pad + y * w + x] = w_host[(((size_t)r * n_regions + g) * H0 + (size_t)y * fy) * W0 + (size_t)x * fx];
+        CFGPP_HIP_CHECK(hipMemcpy(u->d_region_w[l], lvl_w.data(), lvl_w.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    u->regions = 0; u->region_map_rows = 0;                    // exclusive with the hard id map
+    u->soft_regions = n_regions; u->soft_map_rows = map_rows;
     u->retag_cross();
     return 0;
 }
 
 // what a forward / profile needs of the regional state (by name, with both numbers)
 static int regions_ready(const cfgpp_unet* u, int rows, const char* who) {
+    if (u->soft_regions) {
+        if (u->ctx_tokens != 77 * u->soft_regions) {
+            cfgpp_set_error("%s: region weights are on with n_regions=%d (a context of %d tokens) but the context has tokens=%d", who, u->soft_regions,
+                            77 * u->soft_regions, u->ctx_tokens);
+            return -2;
+        }
+        if (u->soft_map_rows != 1 && u->soft_map_rows != rows) {
+            cfgpp_set_error("%s: the region weights were set for map_rows=%d, the call runs rows=%d (1 or rows)", who, u->soft_map_rows, rows);
+            return -2;
+        }
+        return 0;
+    }
     if (!u->regions) return 0;
     if (u->ctx_tokens != 77 * u->regions) {
         cfgpp_set_error("%s: regions are on with n_regions=%d (a context of %d tokens) but the context has tokens=%d", who, u->regions, 77 * u->regions,
@@ -1493,6 +1590,8 @@ int cfgpp_sample_graph_ddim(cfgpp_unet* u, void* z, void* z0t, int z_is_half, in
                                             "(cfgpp_unet_attach_control(u, NULL, 0)) or run the eager loop");
     CFGPP_REQUIRE(!u->regions, "sample_graph: regional prompts are on (cfgpp_unet_set_regions, n_regions=%d): a region-masked step is not captured, "
                                 "run the eager loop", u->regions);
+    CFGPP_REQUIRE(!u->soft_regions, "sample_graph: region weights are on (cfgpp_unet_set_region_weights, n_regions=%d): a region-weighted step is not "
+                                     "captured, run the eager loop", u->soft_regions);
     hipStream_t s = (hipStream_t)stream;
     CFGPP_REQUIRE(u->cfg.in_channels == u->cfg.out_channels || (u->cond_rows > 0 && (u->cond_rows == 1 || u->cond_rows == z_rows)),
                   "sample_graph: inpaint UNet (%d input channels) needs cfgpp_unet_image_condition with 1 or z_rows=%d rows first (has %d)",

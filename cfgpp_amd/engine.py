@@ -475,9 +475,9 @@ class HipUNet:
     """Hand-written HIP UNet behind the C ABI.  One instance per device."""
 
     def __init__(self, cfg: UNetConfig, max_rows: int, sample_hw: Optional[Tuple[int, int]] = None,
-                 device: int = 0, max_tokens: int = 77):
+                 device: int = 0, max_tokens: int = 77, soft_regions: bool = False):
         """``max_tokens``: the longest text context ``set_context`` will take, 77 * j with j <= 4 (include/cfgpp_long_prompt.h:
-        cfgpp_unet_set_max_tokens)"""
+        cfgpp_unet_set_max_tokens).  ``soft_regions``: also allocate the region-weight buffers (``enable_region_weights``)"""
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise CfgppError("HipUNet needs a ROCm GPU (torch.cuda.is_available() is False); "
@@ -496,6 +496,10 @@ class HipUNet:
         self.max_tokens = 77
         if int(max_tokens) != 77:
             self.set_max_tokens(max_tokens)
+        self.soft_regions_enabled = False
+        self.soft_regions = 0                        # n_regions while region weights are set (set_region_weights)
+        if soft_regions:
+            self.enable_region_weights()
         self.time_cond = 0                           # time_cond_proj_dim of a guidance-embedded UNet (include/cfgpp_lcm.h)
         if int(getattr(cfg, "time_cond_proj_dim", 0)):
             self.set_time_cond(cfg.time_cond_proj_dim)
@@ -597,6 +601,34 @@ class HipUNet:
         host = ids.detach().to("cpu", torch.uint8).contiguous()
         check(self.lib.cfgpp_unet_set_regions(self._h, host.data_ptr(), int(host.shape[0]), int(n_regions)), "cfgpp_unet_set_regions")
         self.regions = int(n_regions)
+        self.soft_regions = 0            # exclusive: the engine cleared its region weights
+        return self
+
+    def enable_region_weights(self):
+        """before ``finalize``, after ``set_max_tokens`` (> 77): allocate the per-level fp32 region-weight buffers at finalize
+        (include/cfgpp_regions_soft.h: cfgpp_unet_enable_region_weights)"""
+        check(self.lib.cfgpp_unet_enable_region_weights(self._h), "cfgpp_unet_enable_region_weights")
+        self.soft_regions_enabled = True
+        return self
+
+    def set_region_weights(self, w: Optional[torch.Tensor]):
+        """soft regional prompts on the finalized engine (include/cfgpp_regions_soft.h: cfgpp_unet_set_region_weights): ``w`` is a
+        float map [1 or rows, R, H, W], R = 2 .. 4, every pixel's weights summing to 1, and the context to follow holds R chunks of
+        77 tokens.  ``None`` turns the weights off.  Setting weights clears a hard region map and the reverse."""
+        if w is None:
+            check(self.lib.cfgpp_unet_set_region_weights(self._h, None, 0, 0), "cfgpp_unet_set_region_weights")
+            self.soft_regions = 0
+            return self
+        w = torch.as_tensor(w)
+        if w.dim() == 3:
+            w = w[None]
+        if w.dim() != 4 or tuple(w.shape[2:]) != (self.H, self.W) or not w.is_floating_point():
+            raise CfgppError(f"set_region_weights: weights of shape {tuple(w.shape)}, expected a float [1 or rows, R, {self.H}, {self.W}]")
+        host = w.detach().to("cpu", torch.float32).contiguous()
+        check(self.lib.cfgpp_unet_set_region_weights(self._h, host.data_ptr(), int(host.shape[0]), int(host.shape[1])),
+              "cfgpp_unet_set_region_weights")
+        self.soft_regions = int(host.shape[1])
+        self.regions = 0
         return self
 
     def image_condition(self, cond: torch.Tensor):

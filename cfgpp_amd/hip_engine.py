@@ -28,9 +28,10 @@ class HipEngine:
     so there is one stream."""
 
     def __init__(self, cfg: UNetConfig, max_batch: int = 1, latent_hw: Optional[Tuple[int, int]] = None,
-                 device=None, weights="synthetic", weight_seed: int = 0, max_tokens: int = 77):
+                 device=None, weights="synthetic", weight_seed: int = 0, max_tokens: int = 77, soft_regions: bool = False):
         """``max_tokens``: the longest text context (77 * j, j <= 4) the UNet - and a ControlNet built by ``build_controlnet`` -
-        accepts; 77 is the default engine, bit for bit"""
+        accepts; 77 is the default engine, bit for bit.  ``soft_regions``: the UNet also allocates its region-weight buffers
+        (``set_region_weights``; needs max_tokens > 77); False is the engine without them, byte for byte"""
         if isinstance(cfg, str):
             cfg = CONFIGS[cfg]
         if not torch.cuda.is_available():
@@ -46,7 +47,9 @@ class HipEngine:
         # workspaces and every launch run against the current device, and none of the C entry points carries a device guard.
         torch.cuda.set_device(self.device)
         self.max_tokens = int(max_tokens)
-        self.unet = E.HipUNet(cfg, max_rows=2 * self.max_batch, sample_hw=latent_hw, device=self.device.index, max_tokens=self.max_tokens)
+        self.soft_regions = bool(soft_regions)
+        self.unet = E.HipUNet(cfg, max_rows=2 * self.max_batch, sample_hw=latent_hw, device=self.device.index, max_tokens=self.max_tokens,
+                              soft_regions=self.soft_regions)
         if weights == "synthetic":
             items = synth_state_dict_iter(cfg, weight_seed)
         elif isinstance(weights, str):
@@ -182,7 +185,7 @@ class HipEngine:
         are on the loops stay eager."""
         if ids is None:
             if self._regions:
-                self.unet.set_regions(None)
+                self.unet.set_region_weights(None) if self.unet.soft_regions else self.unet.set_regions(None)
             self._regions = 0
             return self
         if self._control is not None:
@@ -194,6 +197,29 @@ class HipEngine:
             ids = torch.cat([ids, ids], 0)
         self.unet.set_regions(ids, int(n_regions))
         self._regions = int(n_regions)
+        return self
+
+    def set_region_weights(self, w: Optional[torch.Tensor]):
+        """soft regional prompts: weights ``w`` [1 or B, R, H, W] (float, every pixel summing to 1; R = 2 .. 4) for the contexts to
+        follow, whose uc / c hold R chunks of 77 tokens; None: off (include/cfgpp_regions_soft.h: cfgpp_unet_set_region_weights).
+        The unconditional rows use the same weights.  Needs an engine built with ``soft_regions=True``.  While on the loops stay
+        eager; weights and a hard region map are exclusive."""
+        if w is None:
+            if self._regions:
+                self.unet.set_region_weights(None) if self.unet.soft_regions else self.unet.set_regions(None)
+            self._regions = 0
+            return self
+        if not self.soft_regions:
+            raise CfgppError("set_region_weights: the engine was built without soft_regions=True (get_solver(..., max_regions=R, soft_regions=True))")
+        if self._control is not None:
+            raise CfgppError("set_region_weights: a ControlNet is set (control_image with regions is not built)")
+        if self._ip is not None:
+            raise CfgppError("set_region_weights: an IP-Adapter is loaded (ip_adapter with regions is not built)")
+        w = torch.as_tensor(w)
+        if w.dim() == 4 and int(w.shape[0]) > 1:
+            w = torch.cat([w, w], 0)
+        self.unet.set_region_weights(w)
+        self._regions = int(self.unet.soft_regions)
         return self
 
     @property

@@ -65,8 +65,11 @@ def controlled(sample):
             raise ValueError(f"{type(self).__name__}.sample() does not take ip_adapter_image_embeds / ip_adapter_image: IP-Adapter image "
                              "prompts are for the text-to-image solvers (inversion, edit and inpaint solvers refuse them)")
         # sample(..., region_prompts=[p1, ..], region_masks=[m1, ..]): regional prompts (cfgpp_amd/regions.py); empty = the plain call
-        if "region_prompts" in kwargs or "region_masks" in kwargs:
-            self._region_job = self._regions_prepare(kwargs.pop("region_prompts", None), kwargs.pop("region_masks", None), image, ip)
+        # region_base_ratio=beta and region_negative_prompts=[n1, ..] go with them (soft masks need get_solver(..., soft_regions=True))
+        if any(k in kwargs for k in ("region_prompts", "region_masks", "region_base_ratio", "region_negative_prompts")):
+            self._region_job = self._regions_prepare(kwargs.pop("region_prompts", None), kwargs.pop("region_masks", None), image, ip,
+                                                     base_ratio=kwargs.pop("region_base_ratio", 0.0),
+                                                     negative_prompts=kwargs.pop("region_negative_prompts", None))
         self._ip_job = self._ip_prepare(ip, ip_scale)
         lora_scale = kwargs.pop("lora_scale", None)
         if lora_scale is not None:          # shorthand: every adapter of the solver at this scale, from this job on
@@ -139,6 +142,10 @@ class StableDiffusion:
             if not self.controllable:
                 raise ValueError(f"max_regions={self.max_regions}: {type(self).__name__} takes no regional prompts - they are for the "
                                  "text-to-image solvers (inversion, edit, inpaint and panorama solvers refuse them)")
+        # soft regions (float masks, region_base_ratio): the engine also carries fp32 weight maps and runs the soft regional kernel
+        self.soft_regions = bool(kwargs.get("soft_regions", False))
+        if self.soft_regions and self.max_regions < 2:
+            raise ValueError(f"soft_regions=True needs max_regions=R with R = 2 .. 4 (max_regions={self.max_regions})")
 
         # what the UNet predicts and on which schedule (DESIGN.md "v-prediction"): "epsilon" / "leading" / no rescaling are the
         # reference's models, bit for bit
@@ -173,7 +180,8 @@ class StableDiffusion:
             from .hip_engine import HipEngine
             engine = HipEngine(cfg, max_batch=self.max_batch, latent_hw=self.latent_hw, device=device,
                                weights=kwargs.get("unet_weights", "synthetic"), weight_seed=kwargs.get("weight_seed", 0),
-                               max_tokens=77 * max(self.max_prompt_chunks, self.max_regions))
+                               max_tokens=77 * max(self.max_prompt_chunks, self.max_regions),
+                               **(dict(soft_regions=True) if self.soft_regions else {}))
         self.engine = engine
         self.unet = engine
         self.work_device = getattr(engine, "device", torch.device("cpu"))
@@ -486,10 +494,14 @@ class StableDiffusion:
             self._refuse_long_context_when_sharded(max(int(a.shape[1]), int(b.shape[1])))      # (prompt_embeds= comes this way too)
             if job is not None:         # regional prompts: the stacked context, then the map the cross-attentions select by
                 from .regions import stack_context
-                sa = stack_context(a, None, job.embeds)[0] if uc is not None else stack_context(None, a, job.embeds)[1]
-                sb = stack_context(None, b, job.embeds)[1] if c is not None else stack_context(b, None, job.embeds)[0]
+                nk = {} if job.negative_embeds is None else dict(negative_embeds=job.negative_embeds)      # [uc | uc_1 | ..]
+                sa = stack_context(a, None, job.embeds, **nk)[0] if uc is not None else stack_context(None, a, job.embeds)[1]
+                sb = stack_context(None, b, job.embeds)[1] if c is not None else stack_context(b, None, job.embeds, **nk)[0]
                 self._set_context(sa, sb, *extra)
-                self.engine.set_regions(job.ids, job.n_regions)
+                if job.weights is not None:      # soft regions: the weights the cross-attentions blend by
+                    self.engine.set_region_weights(job.weights)
+                else:
+                    self.engine.set_regions(job.ids, job.n_regions)
             else:
                 self._set_context(a, b, *extra)
                 if self.max_regions > 1 and getattr(self.engine, "regions", 0):
@@ -508,13 +520,20 @@ class StableDiffusion:
         towers = self.text_encoder if isinstance(self.text_encoder, (tuple, list)) else (self.text_encoder,)
         return torch.cat([enc(as_list(prompt))[0] for enc in towers], dim=-1).to(self.work_device, torch.float16)
 
-    def _regions_prepare(self, region_prompts, region_masks, control_image=None, ip=None):
-        """the region job of one sample() call, or None for a plain call (empty lists): refusals by name, the region map, the
-        region prompts' hidden states"""
+    def _regions_prepare(self, region_prompts, region_masks, control_image=None, ip=None, base_ratio=0.0, negative_prompts=None):
+        """the region job of one sample() call, or None for a plain call (empty lists): refusals by name, the region map (or, on a
+        soft_regions solver, the region weights), the hidden states of the region prompts and of their negative prompts"""
         from . import regions as RG
         R = RG.check_lists(region_prompts, region_masks, self.max_regions if self.max_regions > 1 else RG.MAX_REGIONS)
+        beta = RG.check_base_ratio(base_ratio)
         if R == 1:
+            if beta != 0.0 or negative_prompts:
+                raise ValueError("region_base_ratio / region_negative_prompts given without region_prompts")
             return None
+        if beta != 0.0 and not getattr(self, "soft_regions", False):
+            raise ValueError(f"region_base_ratio={beta:g} needs a soft-regions solver: get_solver(..., max_regions=R, soft_regions=True) "
+                             "(with soft_regions=False the masks are binarized into a hard partition and the ratio must be 0)")
+        negatives = RG.check_negatives(negative_prompts, R - 1)
         if not self.controllable:
             raise ValueError(f"{type(self).__name__}.sample() does not take region_prompts: regional prompts are for the text-to-image "
                              "solvers (inversion, edit, inpaint and panorama solvers refuse them)")
@@ -533,9 +552,17 @@ class StableDiffusion:
             raise ValueError(f"region_prompts: the engine {type(self.engine).__name__} has no set_regions")
         embeds = tuple(self._region_hidden(p) for p in region_prompts)
         B = max(int(e.shape[0]) for e in embeds)
-        ids = RG.build_region_map(list(region_masks), self.latent_hw, B if B > 1 else None)     # (B = 1: the engine checks the rows)
+        neg = None if negatives is None else tuple(None if n is None else self._region_hidden(n) for n in negatives)
         self._region_serial += 1
-        return RG.RegionJob(ids, embeds, self._region_serial)
+        if getattr(self, "soft_regions", False):
+            if not hasattr(self.engine, "set_region_weights"):
+                raise ValueError(f"soft_regions: the engine {type(self.engine).__name__} has no set_region_weights")
+            w = RG.build_region_weights(list(region_masks), self.latent_hw, B if B > 1 else None, beta)
+            return RG.RegionJob(None, embeds, self._region_serial, w, neg)
+        ids = RG.build_region_map(list(region_masks), self.latent_hw, B if B > 1 else None)     # (B = 1: the engine checks the rows)
+        if neg is None:
+            return RG.RegionJob(ids, embeds, self._region_serial)
+        return RG.RegionJob(ids, embeds, self._region_serial, None, neg)
 
     # ------------------------------------------------------------------ the DDIM step rule; whole-loop graph replay
     def _ddim_step_coeffs(self, t, inversion: bool, wrap: bool):

@@ -58,6 +58,15 @@ def main(argv=None, solver_kwargs=None) -> None:
                     help="regional prompts: size the engine for up to this many regions (the prompt is region 0; 1 = off)")
     ap.add_argument("--region", action="append", default=[], metavar="X0,Y0,X1,Y1:PROMPT",
                     help="repeatable: a rectangle as fractions of width and height, and the prompt that applies inside it (later ones win)")
+    ap.add_argument("--soft_regions", action="store_true",
+                    help="regions blend by per-pixel weights (soft masks, --region_feather, --region_base_ratio) on the soft regional kernel")
+    ap.add_argument("--region_feather", type=float, default=0.0, metavar="F",
+                    help="--soft_regions: width of the linear ramp on every rectangle edge, as a fraction of the shorter side "
+                         "(edges on the image border ramp too: a region touching the border fades to the base prompt there)")
+    ap.add_argument("--region_base_ratio", type=float, default=0.0, metavar="B",
+                    help="--soft_regions: this fraction of the base prompt everywhere, the regions share the rest")
+    ap.add_argument("--region_negative", action="append", default=[], metavar="I:PROMPT",
+                    help="repeatable: a negative prompt of its own for the I-th --region (1-based); the others keep --null_prompt")
     ap.add_argument("--lora", action="append", default=[], metavar="PATH[:SCALE]",
                     help="LoRA safetensors file merged into the UNet on the device (repeatable; scale defaults to 1)")
     ap.add_argument("--ip_adapter", default=None, metavar="PATH[:SCALE]",
@@ -108,6 +117,12 @@ def main(argv=None, solver_kwargs=None) -> None:
         kw["max_prompt_chunks"] = args.max_prompt_chunks
     if args.max_regions > 1:
         kw["max_regions"] = args.max_regions
+    if args.soft_regions:
+        if args.max_regions < 2:
+            raise SystemExit("--soft_regions needs --max_regions 2 .. 4")
+        kw["soft_regions"] = True
+    elif args.region_feather or args.region_base_ratio:
+        raise SystemExit("--region_feather / --region_base_ratio need --soft_regions")
     kw.update(solver_kwargs or {})
     prompts = [args.prompt] * args.batch if args.batch > 1 else args.prompt
     seeds = None if args.batch == 1 else [args.seed + i for i in range(args.batch)]   # B = 1: global CPU RNG, like the reference
@@ -152,7 +167,19 @@ def _region_kwargs(args, solver):
     if args.max_regions < 1 + len(args.region):
         raise SystemExit(f"--region given {len(args.region)} times: needs --max_regions {1 + len(args.region)} (the prompt is region 0; up to 4)")
     parsed = [parse_region(r) for r in args.region]
-    return dict(region_prompts=[p for _, p in parsed], region_masks=[rect_mask(*rect, solver.latent_hw) for rect, _ in parsed])
+    out = dict(region_prompts=[p for _, p in parsed], region_masks=[rect_mask(*rect, solver.latent_hw) for rect, _ in parsed])
+    if getattr(args, "soft_regions", False):
+        from cfgpp_amd.regions import soft_rect_mask
+        out["region_masks"] = [soft_rect_mask(*rect, solver.latent_hw, getattr(args, "region_feather", 0.0)) for rect, _ in parsed]
+        out["region_base_ratio"] = getattr(args, "region_base_ratio", 0.0)
+    if getattr(args, "region_negative", None):
+        from cfgpp_amd.regions import parse_region_negative
+        neg = [None] * len(parsed)
+        for spec in args.region_negative:
+            i, p = parse_region_negative(spec, len(parsed))
+            neg[i - 1] = p
+        out["region_negative_prompts"] = neg
+    return out
 
 
 def _ip_kwargs(args, kw):
